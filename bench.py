@@ -9,8 +9,12 @@ Contract (driver): `python bench.py --gpus N --steps K --warmup W` prints ONE JS
   value       : tokens/s over the timed K steps, inputs/weights/KV resident in HBM, max over ranks
   N > 1       : tensor parallel over N GPUs (one process per GPU, RCCL all-reduce / all-gather), same batch ->
                 "strong" scaling
-Extra objects: `roofline` (dominant kernel, HIP-event timed inside this script), `cpu_baseline` (C port of the
-reference CPU arithmetic on the host cores), `step` (whole-step algorithmic bytes and achieved GB/s).
+A plain run does only that: set-up, one settle phase, W warm-up steps, exactly K timed steps, the line.  `--dump-outputs DIR`
+also writes what the last timed step returned (DIR/tokens.npy, DIR/logits.npy); the inputs are seeded, so two builds can be
+compared output for output.  `step` (whole-step algorithmic bytes and achieved GB/s) is arithmetic on the headline.
+With `--full`, extra objects: `roofline` (dominant kernel, HIP-event timed inside this script), `cpu_baseline` (C port of the
+reference CPU arithmetic on the host cores), `batch32`, `prefill`, `configs`, `parity`, `experiments`; `value` is then the
+median of three timed blocks.
 Synthetic data: random-init weights of the named architecture in Q4_K_M mixture, random KV prefix.
 """
 import argparse
@@ -42,7 +46,15 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=128)
     ap.add_argument("--warmup", type=int, default=16)
-    ap.add_argument("--blocks", type=int, default=3, help="timed blocks of --steps steps each; the value is the median block")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline: everything else this script measures or checks (first greedy tokens, per-launch-group roofline, "
+                         "batch 32, prompt step, the BASELINE configs[2..4] legs, full-size parity against the oracle, the kernel A/B, the CPU "
+                         "baselines), and three timed blocks instead of one.  Without it a run sets up, warms up, times --steps steps and prints")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy: `tokens` (the greedy tokens the "
+                         "step hands back, float64 [batch]) and, on one GPU, `logits` (the step's logits, float32 [batch, vocab])")
+    ap.add_argument("--blocks", type=int, default=None, help="timed blocks of --steps steps each; the value is the median block "
+                                                             "(default: 1, with --full 3)")
     ap.add_argument("--settle-steps", type=int, default=160, help="N > 1 only: untimed steps before the first block (every rank must run the "
                                                                    "same number of steps, so the time criterion of N = 1 cannot be used)")
     ap.add_argument("--batch", type=int, default=1)
@@ -390,6 +402,23 @@ def parity_leg(mode):
     return out
 
 
+def dump_outputs(path, tokens, logits):
+    """--dump-outputs: what the last timed step handed back, one .npy per array: `tokens` float64 [batch] (the greedy tokens read back
+    by the step) and `logits` float32 [batch, vocab] (the step's logits in the model's device buffer; None under tensor parallelism).
+    Logits beyond 48 MB (batch > 98 at this vocabulary) are cut to a fixed, seeded sample of columns, written as `logits_columns`."""
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "tokens.npy"), np.asarray(tokens, np.float64))
+    if logits is None:
+        return
+    logits = np.ascontiguousarray(logits, np.float32)
+    cap = 48 * 1024 * 1024 // (4 * logits.shape[0])
+    if logits.shape[1] > cap:
+        cols = np.sort(np.random.default_rng(0).choice(logits.shape[1], cap, replace=False))
+        np.save(os.path.join(path, "logits_columns.npy"), cols.astype(np.float64))
+        logits = np.ascontiguousarray(logits[:, cols])
+    np.save(os.path.join(path, "logits.npy"), logits)
+
+
 def setup_comm(gm, M, dist, args, rank, world):
     """The tensor-parallel communicator of this run, decided by ALL ranks together -> (transport string, fallback communicator or None).
       1. local pre-flight (no collective inside): librccl loadable; not the same-device rehearsal (RCCL refuses two ranks on one GPU);
@@ -484,6 +513,9 @@ def main():
     if args.same_device and world > 1:
         invalid = ((invalid + "; ") if invalid else "") + f"{world} ranks on ONE device: a rehearsal of the multi-GPU control flow, not a scaling measurement"
     B, K, Wm = args.batch, args.steps, args.warmup
+    n_blocks = args.blocks if args.blocks else (3 if args.full else 1)
+    # the pool is sized for the batch-32 measurement with or without --full: the block permutation and the random cache depend on the
+    # pool size, so a plain run and a --full run time the same step on the same inputs
     do_b32 = (not args.no_batch32) and world == 1 and B == 1
     B32 = 32
     blocks_per_seq = -(-(max(args.ctx, 4096 if do_b32 else 0) + max(K, args.b32_steps) + Wm + 2) // cfg.block_size)
@@ -519,9 +551,11 @@ def main():
     def reset():                                              # the greedy loop back at the benchmark's start state (same graph shape)
         gm.decode_begin(tokens, seq_lens, bt, ctx_cap=ctx_cap, stream=st)
 
+    last = {}
+
     def step():
         gm.decode_step(st)
-        gm.read_tokens(st)                                    # greedy sample -> host every step, as the engine does
+        last["tokens"] = gm.read_tokens(st)                   # greedy sample -> host every step, as the engine does
 
     def sync():                                               # the contract's bracket: barrier + device synchronisation
         torch.cuda.synchronize()
@@ -536,20 +570,23 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         return float(t.item())
 
-    # settle by time (fixed count under TP: every step holds collectives), then >= 3 blocks of: reset, W untimed warm-up steps, EXACTLY K
-    # timed steps between barrier + synchronize, max over ranks; `value` = the median block (bench_timing.py)
+    # settle by time (fixed count under TP: every step holds collectives), then one block (--full: three) of: reset, W untimed warm-up
+    # steps, EXACTLY K timed steps between barrier + synchronize, max over ranks; `value` = the median block (bench_timing.py)
     import bench_timing
-    tb = bench_timing.timed_blocks(step, sync, K, warmup=Wm, blocks=args.blocks, reset=reset, stats=gm.graph_stats,
+    tb = bench_timing.timed_blocks(step, sync, K, warmup=Wm, blocks=n_blocks, reset=reset, stats=gm.graph_stats,
                                    fixed_settle_steps=(args.settle_steps if world > 1 else 0), reduce_max=reduce_max)
     dt = tb["median_s"]
     tok_s = B * K / dt
-    # the first greedy tokens of the benchmark's start state (untimed, every rank): a sharded run and the one-GPU run of the same
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last["tokens"], gm.logits_numpy(B) if world == 1 else None)
+    # --full: the first greedy tokens of the benchmark's start state (untimed, every rank): a sharded run and the one-GPU run of the same
     # synthetic model can be compared token by token (tests/test_gpu_tp2.py runs both)
-    reset()
     head_tokens = []
-    for _ in range(min(8, K + Wm)):
-        gm.decode_step(st)
-        head_tokens.append([int(t) for t in gm.read_tokens(st)])
+    if args.full:
+        reset()
+        for _ in range(min(8, K + Wm)):
+            gm.decode_step(st)
+            head_tokens.append([int(t) for t in gm.read_tokens(st)])
 
     # ---- algorithmic bytes of one step: every weight byte once + live KV once (+ the write)
     mean_ctx = args.ctx + 1 + Wm + (K - 1) / 2.0
@@ -566,9 +603,9 @@ def main():
         "config": {"workload": "BASELINE configs[1]: Llama-3-8B Q4_K_M GGUF shapes, greedy decode, "
                                f"batch={B}, prompt ctx {args.ctx} in paged KV (block 64), {K} decode steps",
                    "batch": B, "ctx_start": args.ctx + 1 + Wm, "ctx_end": args.ctx + Wm + K,
-                   "parallelism": f"tp{world}", "graph": bool(graph_mode), "first_tokens": head_tokens,
+                   "parallelism": f"tp{world}", "graph": bool(graph_mode), **({"first_tokens": head_tokens} if args.full else {}),
                    **({"same_device": True} if args.same_device else {}),
-                   "timing": {"blocks_ms_per_step": tb["blocks_ms_per_step"], "value_is": "median block",
+                   "timing": {"blocks_ms_per_step": tb["blocks_ms_per_step"], "value_is": "median block" if n_blocks > 1 else "the one timed block",
                               "tokens_per_s_min": round(B * K / tb["max_s"], 2), "tokens_per_s_max": round(B * K / tb["min_s"], 2),
                               "settle": tb["settle"], "graph_captures_in_timed_region": tb.get("graph_captures_in_timed_region"),
                               "eager_steps_in_timed_region": tb.get("eager_steps_in_timed_region"),
@@ -583,53 +620,54 @@ def main():
     }
     if invalid:
         out["invalid"] = invalid
-    # every rank runs the per-launch-group timing: under TP the groups contain the all-reduce / all-gather, so a
+    # --full, every rank runs the per-launch-group timing: under TP the groups contain the all-reduce / all-gather, so a
     # rank-0-only call would wait for its peers forever
-    roofline = gm.dominant_kernel_roofline(stream, HBM_PEAK_GBS)
+    roofline = gm.dominant_kernel_roofline(stream, HBM_PEAK_GBS) if args.full else None
     if rank == 0:
-        out["roofline"] = roofline
-        # `roofline.frac` describes the DOMINANT launch (the best-behaved one of the step); the whole step's time-weighted fraction
-        # -- every algorithmic byte of the step over the step's time -- rides next to it, in `roofline` and in the contract's `config`
-        out["roofline"]["whole_step_frac"] = out["step"]["frac_of_8TBs"]
-        out["config"]["whole_step_frac_of_8TBs"] = out["step"]["frac_of_8TBs"]
-        out["config"]["dominant_launch_frac_of_8TBs"] = roofline["frac"]
-        if do_b32:
-            out["batch32"] = bench_batch32(gm, cfg, args, perm, blocks_per_seq, stream, kv_per_tok)
-            try:
-                out["prefill"] = bench_prefill(gm, cfg, perm, blocks_per_seq)
-            except Exception as e:                            # secondary number only
-                out["prefill"] = {"error": repr(e)}
-            # BASELINE's metric is "decode tokens/s @ batch=1,32 ...; achieved HBM GB/s vs peak": `value` is the batch-1 number, the
-            # batch-32 number and the prompt-step number ride in `config` so that a record which keeps only the contract keys holds them
-            out["config"]["batch32_tokens_per_s"] = out["batch32"]["value"]
-            out["config"]["batch32_frac_of_8TBs"] = round(out["batch32"]["achieved_GBs"] / HBM_PEAK_GBS, 4)
-            out["config"]["batch1_frac_of_8TBs"] = out["step"]["frac_of_8TBs"]
-            if "value" in out["prefill"]:
-                out["config"]["prompt_2048_tokens_per_s"] = out["prefill"]["value"]
-                out["config"]["prompt_2048_frac_of_dense_f16_peak"] = out["prefill"]["frac_of_2.5PF_dense_f16"]
-        if args.legs != "none" and world == 1 and not args.layers and B == 1:
-            import gc
-            del gm                                            # the legs build their own models
-            gc.collect(); torch.cuda.empty_cache()
-            import bench_legs
-            names = list(bench_legs.LEGS) if args.legs == "all" else [n for n in args.legs.split(",") if n in bench_legs.LEGS]
-            out["configs"] = bench_legs.run_legs(names, parity=args.parity != "off")
-        if args.parity != "off" and world == 1 and not args.layers:
-            try:
-                out["parity"] = parity_leg(args.parity)
-            except Exception as e:                            # the checker must never sink the measured number
-                out["parity"] = {"error": repr(e)}
-        if do_b32 and not args.no_experiments and args.legs != "none" and not args.layers:
-            out["experiments"] = experiments_leg()
-        if not args.no_cpu_baseline and world == 1:
-            try:
-                out["cpu_baseline"] = cpu_baseline(cfg, args.cpu_steps, args.ctx)
-            except Exception as e:                            # the baseline must never sink the GPU number
-                out["cpu_baseline"] = {"error": repr(e)}
-            try:
-                out["cpu_baseline_config0"] = cpu_baseline_config0()
-            except Exception as e:
-                out["cpu_baseline_config0"] = {"error": repr(e)}
+        if args.full:
+            out["roofline"] = roofline
+            # `roofline.frac` describes the DOMINANT launch (the best-behaved one of the step); the whole step's time-weighted fraction
+            # -- every algorithmic byte of the step over the step's time -- rides next to it, in `roofline` and in the contract's `config`
+            out["roofline"]["whole_step_frac"] = out["step"]["frac_of_8TBs"]
+            out["config"]["whole_step_frac_of_8TBs"] = out["step"]["frac_of_8TBs"]
+            out["config"]["dominant_launch_frac_of_8TBs"] = roofline["frac"]
+            if do_b32:
+                out["batch32"] = bench_batch32(gm, cfg, args, perm, blocks_per_seq, stream, kv_per_tok)
+                try:
+                    out["prefill"] = bench_prefill(gm, cfg, perm, blocks_per_seq)
+                except Exception as e:                            # secondary number only
+                    out["prefill"] = {"error": repr(e)}
+                # BASELINE's metric is "decode tokens/s @ batch=1,32 ...; achieved HBM GB/s vs peak": `value` is the batch-1 number, the
+                # batch-32 number and the prompt-step number ride in `config` so that a record which keeps only the contract keys holds them
+                out["config"]["batch32_tokens_per_s"] = out["batch32"]["value"]
+                out["config"]["batch32_frac_of_8TBs"] = round(out["batch32"]["achieved_GBs"] / HBM_PEAK_GBS, 4)
+                out["config"]["batch1_frac_of_8TBs"] = out["step"]["frac_of_8TBs"]
+                if "value" in out["prefill"]:
+                    out["config"]["prompt_2048_tokens_per_s"] = out["prefill"]["value"]
+                    out["config"]["prompt_2048_frac_of_dense_f16_peak"] = out["prefill"]["frac_of_2.5PF_dense_f16"]
+            if args.legs != "none" and world == 1 and not args.layers and B == 1:
+                import gc
+                del gm                                            # the legs build their own models
+                gc.collect(); torch.cuda.empty_cache()
+                import bench_legs
+                names = list(bench_legs.LEGS) if args.legs == "all" else [n for n in args.legs.split(",") if n in bench_legs.LEGS]
+                out["configs"] = bench_legs.run_legs(names, parity=args.parity != "off")
+            if args.parity != "off" and world == 1 and not args.layers:
+                try:
+                    out["parity"] = parity_leg(args.parity)
+                except Exception as e:                            # the checker must never sink the measured number
+                    out["parity"] = {"error": repr(e)}
+            if do_b32 and not args.no_experiments and args.legs != "none" and not args.layers:
+                out["experiments"] = experiments_leg()
+            if not args.no_cpu_baseline and world == 1:
+                try:
+                    out["cpu_baseline"] = cpu_baseline(cfg, args.cpu_steps, args.ctx)
+                except Exception as e:                            # the baseline must never sink the GPU number
+                    out["cpu_baseline"] = {"error": repr(e)}
+                try:
+                    out["cpu_baseline_config0"] = cpu_baseline_config0()
+                except Exception as e:
+                    out["cpu_baseline_config0"] = {"error": repr(e)}
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.barrier()

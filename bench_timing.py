@@ -6,7 +6,7 @@ run reported half the rate of every other run.  Now every timed number is taken 
 
   1. settle by TIME: replay the step (each step ends in the token read-back, i.e. a stream synchronisation) until at least `settle_ms`
      of GPU work have run AND three consecutive step times agree within `agree` (2 %); capped, and the line says whether it settled;
-  2. `blocks` (>= 3) timed blocks of EXACTLY `steps` steps each, every block from the same start state (the caller's `reset`: the greedy
+  2. `blocks` (three; one for bench.py's headline without --full) timed blocks of EXACTLY `steps` steps each, every block from the same start state (the caller's `reset`: the greedy
      loop is re-begun at the same context, then `warmup` untimed steps), bracketed by a device synchronisation on both sides;
   3. the reported value is the MEDIAN block; min, max and every block ride along, together with the library's capture / eager-step
      counters before and after the timed region (mi355_llama_graph_captures: a re-capture inside a timed block would be visible).

@@ -28,7 +28,7 @@ def _free_port():
     return p
 
 
-def _worker(rank, world, port, q):
+def _worker(rank, world, port, q, extra=("--full",)):
     try:
         os.environ.update({"RANK": str(rank), "LOCAL_RANK": str(rank), "WORLD_SIZE": str(world),
                            "MASTER_ADDR": "127.0.0.1", "MASTER_PORT": str(port)})
@@ -37,7 +37,7 @@ def _worker(rank, world, port, q):
         from tests import bench_standin
         bench_standin.install(calls)
         import bench
-        sys.argv = ["bench.py", "--gpus", str(world), "--steps", "3", "--warmup", "2", "--settle-steps", "4"]
+        sys.argv = ["bench.py", "--gpus", str(world), "--steps", "3", "--warmup", "2", "--settle-steps", "4"] + list(extra)
         buf, old = io.StringIO(), sys.stdout
         sys.stdout = buf
         try:
@@ -50,12 +50,11 @@ def _worker(rank, world, port, q):
         raise
 
 
-@pytest.mark.timeout(300)
-def test_bench_main_two_ranks_control_flow():
+def _run_two_ranks(extra):
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
     port = _free_port()
-    procs = [ctx.Process(target=_worker, args=(r, 2, port, q)) for r in range(2)]
+    procs = [ctx.Process(target=_worker, args=(r, 2, port, q, extra)) for r in range(2)]
     for p in procs:
         p.start()
     res = {}
@@ -69,6 +68,12 @@ def test_bench_main_two_ranks_control_flow():
             p.join(timeout=30)
             if p.is_alive():
                 p.terminate()                            # this test's own children only
+    return res
+
+
+@pytest.mark.timeout(300)
+def test_bench_main_two_ranks_control_flow():
+    res = _run_two_ranks(("--full",))
     out0, calls0 = res[0]
     out1, calls1 = res[1]
     assert out1.strip() == ""                            # only rank 0 prints
@@ -88,6 +93,33 @@ def test_bench_main_two_ranks_control_flow():
         assert ("init_comm", "auto") in calls and ("roofline",) in calls and ("graph", True) in calls
         assert calls.count(("step",)) == 4 + 3 * 5 + 5   # 4 settle steps, 3 blocks of (2 warm-up + 3 timed), 5 untimed steps for `first_tokens`, on every rank
     assert calls0[0] == ("create", 0, 2, 1) and calls1[0] == ("create", 1, 2, 1)
+
+
+@pytest.mark.timeout(300)
+def test_bench_main_two_ranks_plain_run_is_lean(tmp_path):
+    """without --full: settle, ONE block of warm-up + exactly --steps timed steps, the line -- no roofline sweep, no extra greedy steps, no
+    secondary objects; --dump-outputs writes what the last timed step returned (rank 0 only; the logits are a one-GPU output)"""
+    res = _run_two_ranks(("--dump-outputs", str(tmp_path / "dump")))
+    out0, calls0 = res[0]
+    out1, calls1 = res[1]
+    assert out1.strip() == ""
+    lines = [ln for ln in out0.splitlines() if ln.strip()]
+    assert len(lines) == 1
+    j = json.loads(lines[0])
+    for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+                "vs_baseline", "dtype", "data", "config"):
+        assert key in j, key
+    for key in ("roofline", "cpu_baseline", "cpu_baseline_config0", "batch32", "prefill", "configs", "parity", "experiments"):
+        assert key not in j, key
+    assert "first_tokens" not in j["config"] and len(j["config"]["timing"]["blocks_ms_per_step"]) == 1
+    assert j["n_gpus"] == 2 and j["steps"] == 3 and j["warmup"] == 2
+    assert j["value"] > 0 and abs(j["value"] - 1e3 / j["ms_per_step"]) / j["value"] < 1e-2
+    for calls in (calls0, calls1):
+        assert ("roofline",) not in calls
+        assert calls.count(("step",)) == 4 + (2 + 3)     # 4 settle steps, one block of 2 warm-up + 3 timed steps
+    assert sorted(os.listdir(tmp_path / "dump")) == ["tokens.npy"]
+    tok = np.load(tmp_path / "dump" / "tokens.npy")
+    assert tok.dtype == np.float64 and tok.shape == (1,)
 
 
 @pytest.mark.timeout(300)

@@ -538,7 +538,7 @@ def test_bench_py_gpus_2_rehearsed_on_one_device():
     if not torch.cuda.is_available():
         pytest.fail("GPU tests need a visible MI355X")
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    common = ["--layers", "2", "--steps", "6", "--warmup", "2", "--no-batch32", "--no-cpu-baseline", "--parity", "off", "--legs", "none",
+    common = ["--full", "--layers", "2", "--steps", "6", "--warmup", "2", "--no-batch32", "--no-cpu-baseline", "--parity", "off", "--legs", "none",
               "--settle-steps", "6"]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "MI355_BENCH_FAIL_COMM_RANK")}
     env["PYTHONPATH"] = root + os.pathsep + env.get("PYTHONPATH", "")

@@ -3,7 +3,7 @@
 # them to profiles/).  Every file carries the commit it was measured on: write it to ./COMMIT_SHA before the call
 #   git rev-parse --short HEAD > COMMIT_SHA && gpurun --timeout 1500 -- 'bash tools/refresh_profiles.sh'
 #   0. two --pmc passes (FETCH_SIZE, WRITE_SIZE)         -> rNN_pmc_traffic.json   (tools/pmc_traffic.py; copied into profiles/ for step 1)
-#   1. python bench.py                                   -> rNN_bench_default.json
+#   1. python bench.py --full                            -> rNN_bench_default.json
 #   2. rocprofv3 --kernel-trace --stats -- bench (B=1)   -> rNN_bench_b1_kernel_stats.csv (+ the bench line under rocprof)
 #   3. rocprofv3 --kernel-trace --stats -- bench (B=32)  -> rNN_bench_b32_kernel_stats.csv
 #   5. one --pmc pass of the SQ busy counters            -> rNN_pmc_sq_b1.json     (MFMA-busy / VALU-busy of every kernel)
@@ -23,7 +23,7 @@ timeout 300 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d /tmp/pmc_f --output-for
 timeout 300 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d /tmp/pmc_w --output-format csv -- $PMC > $OUT/pmc_w.log 2>&1
 python tools/pmc_traffic.py /tmp/pmc_f /tmp/pmc_w $OUT/${RN}_pmc_traffic.json $SHA
 cp $OUT/${RN}_pmc_traffic.json $R/profiles/${RN}_pmc_traffic.json
-timeout 900 python bench.py > $OUT/${RN}_bench_default.json 2> $OUT/bench_default.err
+timeout 900 python bench.py --full > $OUT/${RN}_bench_default.json 2> $OUT/bench_default.err
 B1="python bench.py --no-batch32 --no-cpu-baseline --parity off --legs none"
 timeout 400 rocprofv3 --kernel-trace --stats -d /tmp/rp_b1 --output-format csv -- $B1 > $OUT/${RN}_bench_b1_under_rocprof.json 2> $OUT/rp_b1.err
 (echo "# commit $SHA : rocprofv3 --kernel-trace --stats -- $B1"; cat $(find /tmp/rp_b1 -name "*kernel_stats.csv" | head -1)) > $OUT/${RN}_bench_b1_kernel_stats.csv
