@@ -7,7 +7,7 @@ import contextlib as _contextlib
 
 
 class TuningKeyUnavailable(RuntimeError):
-    """the key belongs to probe builds (tools/build_probe_lib.sh); the product library honours the ten keys of include/mi355_vllm.h"""
+    """the library honours the ten keys of include/mi355_vllm.h and ignores every other"""
 
 
 @_contextlib.contextmanager

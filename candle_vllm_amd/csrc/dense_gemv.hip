@@ -802,13 +802,10 @@ static int dense_launch_gj(const DenseArgs& a, int gj, int nw, hipStream_t st) {
 }
 
 // ---- the 1..4-token launch of 4-bit weights (dense_small_kernel): -4 = this shape stays on dense_kernel
-static int g_tune_gemm_min_t = 96;     // tuning key 36: tokens from which a 16-bit projection takes the 128 x 128 MFMA GEMM
-static int g_tune_gptq_gemm_off = 0;   // tuning key 39: 1 = 4-bit prompt steps run the decode kernel in 64-token chunks (A/B)
-static int g_tune_wide_nw = 4;         // tuning key 38: waves (row tiles) per workgroup of dense_wide_kernel: 2 | 4
-static int g_tune_wide_off = 0;        // tuning key 37: 1 = 16-bit launches with many row tiles stay on dense_kernel (A/B)
-static int g_tune_small_nw = 0;        // tuning key 30: waves per workgroup (0 = chosen from the k-blocks)
-static int g_tune_small_nw_big = 0;    // tuning key 35: the same for K > 8192
-static int g_tune_gemm_tall = 0;       // tuning key 30 bit 32 (round 4; measured SLOWER, stays off: bf16 prompt step of Llama-3-8B 53.7 k -> 51.5 k tok/s): the 256-token tile of the 16-bit prompt GEMM where it fills the chip twice
+#define DENSE_GEMM_MIN_T 96            // tokens from which a 16-bit or tiled 4-bit projection takes its MFMA GEMM
+static int g_tune_gptq_gemm_off = 0;   // tuning key 30 bit 16: 1 = 4-bit prompt steps run the decode kernel in 64-token chunks (A/B)
+static int g_tune_wide_off = 0;        // tuning key 30 bit 8: 1 = 16-bit launches with many row tiles stay on dense_kernel (A/B)
+static int g_tune_gemm_tall = 0;      // tuning key 30 bit 32 (round 4; measured SLOWER, stays off: bf16 prompt step of Llama-3-8B 53.7 k -> 51.5 k tok/s): the 256-token tile of the 16-bit prompt GEMM where it fills the chip twice
 static int g_tune_small_off = 0;       // tuning key 31: 1 = keep 1..4 tokens on dense_kernel (A/B measurements)
 static int g_tune_gptq_wide_nosplit = 0;   // tuning key 30 bit 256: gate/up pairs of the 5..32-token 4-bit launches stay on one wave each (A/B)
 static int g_tune_gptq_wide_off = 0;   // tuning key 30 bit 128: 1 = 5..64-token launches of tiled 4-bit weights stay on dense_kernel (A/B; round 5)
@@ -817,27 +814,18 @@ static int g_tune_small_nonorm = 0;    // tuning key 32: 1 = never norm on the w
 // tuning key 30 (product): bit mask of folded launches switched OFF -- 1 = the 1..4-token 4-bit kernel, 2 = no norm on the way in,
 // 4 = RoPE and the cache write in their own launch, 8 = the LDS-shared-activation 16-bit kernel, 16 = the one-pass 4-bit prompt GEMM;
 // 32 (switches ON) = the 256-token tile of the 16-bit prompt GEMM where it fills the chip twice, 32 | 64 = wherever that GEMM runs (tests).
-// Probe builds: 33 / 35 waves per workgroup of the 1..4-token kernel (hidden-sized K / long K), 36 tokens from which 16-bit
-// projections take the MFMA GEMM, 38 waves per workgroup of the LDS-shared-activation kernel.
 void mi355_dense_set_small(int key, int v) {
-    if (key == 30) {
-        g_tune_small_off = v & 1; g_tune_small_nonorm = (v >> 1) & 1; g_tune_small_norope = (v >> 2) & 1;
-        g_tune_wide_off = (v >> 3) & 1; g_tune_gptq_gemm_off = (v >> 4) & 1; g_tune_gemm_tall = (v >> 5) & 3;
-        g_tune_gptq_wide_off = (v >> 7) & 1;
-        g_tune_gptq_wide_nosplit = (v >> 8) & 1;
-    }
-    else if (key == 33) g_tune_small_nw = v;
-    else if (key == 35) g_tune_small_nw_big = v;
-    else if (key == 36 && v > 0) g_tune_gemm_min_t = v;
-    else if (key == 38) g_tune_wide_nw = v;
+    if (key != 30) return;
+    g_tune_small_off = v & 1; g_tune_small_nonorm = (v >> 1) & 1; g_tune_small_norope = (v >> 2) & 1;
+    g_tune_wide_off = (v >> 3) & 1; g_tune_gptq_gemm_off = (v >> 4) & 1; g_tune_gemm_tall = (v >> 5) & 3;
+    g_tune_gptq_wide_off = (v >> 7) & 1;
+    g_tune_gptq_wide_nosplit = (v >> 8) & 1;
 }
 static inline int dense_small_gj(int group_size) {
     if (group_size >= 256) return (group_size % 256) ? -1 : 8;
     return group_size == 128 ? 4 : group_size == 64 ? 2 : group_size == 32 ? 1 : -1;
 }
 static inline int dense_small_nw(int nkb) {
-    if (g_tune_small_nw >= 1 && g_tune_small_nw <= 8 && g_tune_small_nw <= nkb && nkb <= 32) return g_tune_small_nw;   // experiments: hidden-sized K only
-    if (g_tune_small_nw_big >= 1 && g_tune_small_nw_big <= 8 && nkb > 32) return g_tune_small_nw_big;
     if (nkb < 4) return nkb;
     // hidden-sized K (<= 16 k-blocks: 4096): four waves -- more, smaller workgroups per CU balance the launch better than more
     // waves on fewer (Qwen2-7B gate/up, 1184 workgroups: 19.5 us with 2..4 waves, 22.3 us with 7; q/k/v and wo within 0.4 us)
@@ -949,7 +937,7 @@ static int dense_launch_dt(const DenseArgs& a, hipStream_t st) {
         const bool many = wtiles >= 4 * 192, longk = !pair && nkb_w >= 32 && mt <= 3;
         if (!g_tune_wide_off && a.T > 4 && (many || longk) && (!pair || mt <= 2) && !((uintptr_t)a.x & 15) && !(a.ldx & 7) &&
             !((uintptr_t)a.w & 15) && (a.wtiled || !(a.ldw & 7))) {
-            const int nwv = many ? (g_tune_wide_nw == 2 ? 2 : 4) : 4;
+            constexpr int nwv = 4;                                      // waves (row tiles) per workgroup
             const int gx = (wtiles + nwv - 1) / nwv;
             int ks = 1;
             if (!many) {
@@ -969,14 +957,12 @@ static int dense_launch_dt(const DenseArgs& a, hipStream_t st) {
             }
             const dim3 grid(gx, ks), block(64 * nwv);
             const size_t lds = (size_t)2 * mt * 16 * DWD_LDX * 2;
-#define DWD_GO2(MT_, R_, NW_) do { \
+#define DWD_GO(MT_, R_) do { \
                 static bool attr = false; \
-                if (!attr) { (void)hipFuncSetAttribute((const void*)dense_wide_kernel<DT, MT_, R_, NW_>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024); attr = true; } \
-                hipLaunchKernelGGL((dense_wide_kernel<DT, MT_, R_, NW_>), grid, block, lds, st, a, part, ldp, kps); } while (0)
-#define DWD_GO(MT_, R_) do { if (nwv == 2) DWD_GO2(MT_, R_, 2); else DWD_GO2(MT_, R_, 4); } while (0)
+                if (!attr) { (void)hipFuncSetAttribute((const void*)dense_wide_kernel<DT, MT_, R_, nwv>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024); attr = true; } \
+                hipLaunchKernelGGL((dense_wide_kernel<DT, MT_, R_, nwv>), grid, block, lds, st, a, part, ldp, kps); } while (0)
             if (pair) { if (mt == 1) DWD_GO(1, 2); else DWD_GO(2, 2); }
             else switch (mt) { case 1: DWD_GO(1, 1); break; case 2: DWD_GO(2, 1); break; case 3: DWD_GO(3, 1); break; default: DWD_GO(4, 1); break; }
-#undef DWD_GO2
 #undef DWD_GO
             if (hipGetLastError() != hipSuccess) return -1;
             if (ks > 1) {
@@ -1495,11 +1481,11 @@ static int dense_prompt_gemm(const DenseArgs& a, int dt, hipStream_t st) {
 
 // SILU_MUL with more than 32 tokens, or any T > 64: run in token chunks
 static int dense_run(DenseArgs a, int wtype, int dt, hipStream_t st) {
-    if (wtype == DW_DENSE && a.T >= g_tune_gemm_min_t) {
+    if (wtype == DW_DENSE && a.T >= DENSE_GEMM_MIN_T) {
         const int rc = dense_prompt_gemm(a, dt, st);
         if (rc != (int)hipErrorNotSupported) return rc;                    // odd strides / K: keep streaming in token chunks
     }
-    if (wtype == DW_GPTQ4T && a.T >= g_tune_gemm_min_t) {
+    if (wtype == DW_GPTQ4T && a.T >= DENSE_GEMM_MIN_T) {
         const int rc = gptq_prompt_gemm(a, dt, st);
         if (rc != (int)hipErrorNotSupported) return rc;                    // groups of 32, odd strides: token chunks of the decode kernel
     }

@@ -49,7 +49,6 @@ extern "C" int mi355_pa_stream_auto(int32_t num_seqs, int32_t num_heads, int32_t
 extern "C" int mi355_host_get_partition_override();   // host_model.cpp: mi355_set_tuning(5, partition_size), experiments
 
 namespace {
-int g_dense_tile = 1;          // tuning key 42: 0 = the 16-bit host layer keeps its projections row-major (A/B; read at the first step)
 
 #define DCHECK(expr) do { const int rc_ = (expr); if (rc_ != 0) return rc_; } while (0)
 #define DHIP(expr) do { const hipError_t e_ = (expr); if (e_ != hipSuccess) return (int)e_; } while (0)
@@ -212,7 +211,6 @@ int finalize_weights(DModel* m) {
     if (m->finalized) return 0;
     const mi355_dense_config& c = m->cfg;
     const int hid = c.hidden, HD = c.n_heads * c.head_dim, KD = c.n_kv_heads * c.head_dim, I = c.intermediate;
-    if (!g_dense_tile) { m->finalized = true; return 0; }
     for (auto& L : m->layers) {
         if (L.wq && L.wk && L.wv && !(HD & 15) && !(KD & 15) && !(hid & 255)) {
             DCHECK(tile_one(m, &L.wq, HD, hid)); DCHECK(tile_one(m, &L.wk, KD, hid)); DCHECK(tile_one(m, &L.wv, KD, hid));
@@ -252,8 +250,6 @@ int choose_partition(int batch, int kv_heads, int ctx_cap) {
 }  // namespace
 
 extern "C" {
-
-void mi355_dense_set_tile(int v) { g_dense_tile = v; }
 
 void* mi355_dense_create(const mi355_dense_config* cfg) {
     if (!cfg || cfg->hidden <= 0 || (cfg->hidden % 256) || (cfg->intermediate % 256) || cfg->n_layers <= 0 ||

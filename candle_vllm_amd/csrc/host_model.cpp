@@ -100,7 +100,6 @@ struct Model {
     float* tp_y = nullptr;          // [B, hidden] this rank's o_proj / down_proj partial in the reference's wire mode (bf16 all-reduce)
     float* p_tp_y = nullptr;        // same for prompt steps (grow-only with the prefill workspace)
     float* logits_local = nullptr;  // [B, vocab/W]
-    void* chain_sync = nullptr;     // arrival counters of the chained single-token launches (qmv_chain.inc), zeroed once
     float* logits_gather = nullptr; // [W, B, vocab/W]
     // prefill workspace (grow-only, sized by the largest chunk seen): same roles as xs / q / attn / h
     float* p_xs = nullptr; uint16_t* p_q = nullptr; uint16_t* p_attn = nullptr; float* p_h = nullptr;
@@ -220,8 +219,7 @@ int all_reduce_xs(Model* m, float* xs, float* y, int B, int64_t st) {
 
 enum { PART_QKV = 0, PART_ATTN = 1, PART_WO = 2, PART_GATEUP = 3, PART_DOWN = 4, PART_HEAD = 5, PART_EMBED = 6 };
 
-// The mat-mul descriptor of one dense (non-MoE) launch group, exactly as run_part issues it -- shared with the chained
-// single-token step (run_chain), which hands four of them to ONE persistent launch.
+// The mat-mul descriptor of one dense (non-MoE) launch group, as run_part issues it.
 void dense_desc(Model* m, int l, int part, const StepIn& in, float* logits, mi355_qmm_desc& d) {
     const mi355_llama_config& c = m->cfg;
     const int H = local_heads(m), Hkv = local_kv_heads(m), D = c.head_dim, hid = c.hidden, B = in.B;
@@ -578,22 +576,6 @@ int run_part(Model* m, int l, int part, const StepIn& in, float* logits, int64_t
     return (int)hipErrorInvalidValue;
 }
 
-// Single token, one GPU, dense MLP: the four mat-vecs between two attention calls -- wo + residual, ffn_norm + gate/up +
-// silu*mul, down + residual, then the NEXT layer's attn_norm + q|k|v + RoPE + cache write (or output_norm + lm_head after
-// the last layer) -- run as ONE persistent launch (csrc/qmv_chain.inc).  Returns hipErrorNotSupported when the chain does
-// not apply; the caller then issues the launch groups one by one.
-int run_chain(Model* m, int l, const StepIn& in, float* logits, int64_t st) {
-    const mi355_llama_config& c = m->cfg;
-    if (in.B != 1 || in.is_prefill || m->use_comm || c.n_expert > 1 || !m->chain_sync) return (int)hipErrorNotSupported;
-    mi355_qmm_desc d[4];
-    dense_desc(m, l, PART_WO, in, logits, d[0]);
-    dense_desc(m, l, PART_GATEUP, in, logits, d[1]);
-    dense_desc(m, l, PART_DOWN, in, logits, d[2]);
-    if (l + 1 < c.n_layers) dense_desc(m, l + 1, PART_QKV, in, logits, d[3]);
-    else dense_desc(m, 0, PART_HEAD, in, logits, d[3]);
-    return mi355_qmatmul_chain(d, 4, m->chain_sync, st);
-}
-
 // one decode step over device-resident inputs (everything enqueued on `st`)
 int forward_decode(Model* m, const uint32_t* tokens, const int64_t* positions, const int64_t* slots,
                    const uint32_t* bt, const uint32_t* ctx, int B, int max_blocks, int ctx_cap, float* logits,
@@ -604,24 +586,8 @@ int forward_decode(Model* m, const uint32_t* tokens, const int64_t* positions, c
     const StepIn in{tokens, positions, slots, bt, ctx, B, max_blocks, ctx_cap, m->xs, m->q, m->attn, m->h,
                     m->moe_ids, m->moe_w, m->moe_y, m->tp_y, false, nullptr, 0, 0};
     RCHECK(run_part(m, 0, PART_EMBED, in, logits, st));
-    // single token: embed, q|k|v of layer 0, then per layer [attention, ONE persistent launch for wo -> gate/up -> down ->
-    // the next layer's q|k|v (the lm_head after the last layer)]; any step the chain does not cover falls back group by group
-    bool qkv_done = false, head_done = false;
-    for (int l = 0; l < c.n_layers; ++l) {
-        if (!qkv_done) RCHECK(run_part(m, l, PART_QKV, in, logits, st));
-        RCHECK(run_part(m, l, PART_ATTN, in, logits, st));
-        const int rc = run_chain(m, l, in, logits, st);
-        if (rc == 0) {
-            qkv_done = true;
-            head_done = l + 1 == c.n_layers;
-        } else if (rc == (int)hipErrorNotSupported) {
-            qkv_done = false;
-            for (int part = PART_WO; part <= PART_DOWN; ++part) RCHECK(run_part(m, l, part, in, logits, st));
-        } else {
-            return rc;
-        }
-    }
-    if (head_done) return 0;
+    for (int l = 0; l < c.n_layers; ++l)
+        for (int part = PART_QKV; part <= PART_DOWN; ++part) RCHECK(run_part(m, l, part, in, logits, st));
     return run_part(m, 0, PART_HEAD, in, logits, st);
 }
 
@@ -711,8 +677,6 @@ extern "C" void* mi355_llama_create(const mi355_llama_config* cfg) {
         alloc((void**)&m->logits_local, (size_t)B * padded * 4 / m->cfg.tp_world + 64);
         alloc((void**)&m->logits_gather, (size_t)B * padded * 4 + 64 * m->cfg.tp_world);
     }
-    alloc(&m->chain_sync, (size_t)mi355_qmv_chain_sync_bytes());
-    if (m->chain_sync && hipMemset(m->chain_sync, 0, (size_t)mi355_qmv_chain_sync_bytes()) != hipSuccess) ok = false;
     m->pa_cap_partitions = (cfg->max_seq + 31) / 32 + 1;   // v2 partitions are >= 32 tokens (choose_partition)
     alloc((void**)&m->pa_tmp, (size_t)B * H * m->pa_cap_partitions * D * 4);
     alloc((void**)&m->pa_max, (size_t)B * H * m->pa_cap_partitions * 4);
@@ -772,7 +736,7 @@ extern "C" void mi355_llama_destroy(void* mp) {
     void* ptrs[] = {m->tok_embd, m->output_norm, m->cos_t, m->sin_t, m->xs, m->q, m->attn, m->h, m->logits,
                     m->pa_tmp, m->pa_max, m->pa_sum, m->kv_slab, m->d_tokens, m->d_positions, m->d_slots,
                     m->d_ctx, m->d_bt, m->logits_local, m->logits_gather, m->tp_y, m->p_tp_y, m->p_moe_xg, m->p_moe_perm, m->p_moe_inv, m->p_moe_tab, m->p_xs, m->p_q, m->p_attn, m->p_h,
-                    m->moe_ids, m->moe_w, m->moe_y, m->p_moe_ids, m->p_moe_w, m->p_moe_y, m->chain_sync, m->g_moe_xg, m->g_moe_h, m->g_moe_yg, m->g_moe_pos, m->g_moe_cnt};
+                    m->moe_ids, m->moe_w, m->moe_y, m->p_moe_ids, m->p_moe_w, m->p_moe_y, m->g_moe_xg, m->g_moe_h, m->g_moe_yg, m->g_moe_pos, m->g_moe_cnt};
     if (m->comm && m->comm_owned) mi355_comm_destroy(m->comm);
     for (void* p : ptrs) if (p) (void)hipFree(p);
     delete m;

@@ -200,7 +200,7 @@ struct QmmArgs {
     uint16_t* kcache;
     uint16_t* vcache;
     int32_t Hq, Hkv, D, rot, block_size, kv_layout;
-    int32_t dbg;              // experiments: 1 = stream the weights but skip unpack/MFMA (memory-path probe)
+    int32_t dbg;              // unused (always 0): kept so that the kernel-argument layout stays as it was validated
     // chain request (wide path): the epilogue also stages the activation image of the NEXT mat-mul, whose x is this
     // `out` with k = next_k and RMSNorm weight next_norm_w (or null)
     const float* next_norm_w;
@@ -220,13 +220,6 @@ struct QmmArgs {
 };
 
 struct TileRegs { uint4 a, b, c, d; uint32_t e; };
-// Probe / ablation modes (mi355_set_tuning(2, v)) are compiled into -DMI355_QMM_PROBES builds only (tools/ build their own
-// library): a guarded load or branch in a hot loop costs the production kernels measurable time.
-#ifdef MI355_QMM_PROBES
-#define QMM_DBG(a) ((a).dbg)
-#else
-#define QMM_DBG(a) 0
-#endif
 typedef const void __attribute__((address_space(1)))* qmg_gptr_t;
 typedef void __attribute__((address_space(3)))* qmg_lptr_t;
 // one wave-wide 16-B LDS DMA (lane i lands at lds_dst + 16 i) the compiler does NOT track: the caller counts s_waitcnt vmcnt itself
@@ -638,21 +631,11 @@ __device__ __forceinline__ void qmm_epilogue(const QmmArgs& a, const float* red,
     }
 }
 
-// experiments only (probe mode 7): per-wave timestamps [workgroup][wave 16][4] = entry, main loop done, past the barrier, exit.
-// The hooks are compiled in ONLY with -DMI355_QMM_TIMESTAMPS (tools/exp_wave_times.py builds its own library): four dead
-// scalar branches in the single-token kernel measured 463 vs 485 tok/s at batch 1.
+// where a -DMI355_QMM_TIMELINE build writes its per-wave timestamps (below); the product kernels never read it
 __device__ unsigned long long* g_qmm_ts = nullptr;
 extern "C" int mi355_debug_set_timestamps(void* dev_ptr) {
     return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_qmm_ts), &dev_ptr, sizeof(dev_ptr));
 }
-#ifdef MI355_QMM_TIMESTAMPS
-__device__ __forceinline__ void qmm_stamp(const QmmArgs& a, int i) {
-    if (a.dbg == 7 && (threadIdx.x & 63) == 0 && g_qmm_ts)
-        g_qmm_ts[((size_t)blockIdx.x * 16 + (threadIdx.x >> 6)) * 4 + i] = wall_clock64();
-}
-#else
-#define qmm_stamp(a, i) ((void)0)
-#endif
 // Round 6: the INSIDE of a single-token launch on a timeline (-DMI355_QMM_TIMELINE builds only, tools/exp_b1_timeline.py):
 // eight 100 MHz timestamps per wave, kept in registers and written once at exit (a store in the loop would join the counted vmcnt waits):
 //   0 wave entry   1 kernarg fields in SGPRs   2 every load of the prologue issued   3 first k-block staged (= x and norm weight arrived)
@@ -730,14 +713,10 @@ __device__ __forceinline__ void qmm_burst_vals(T... v) { const int u_[] = {qmm_b
 
 template <int BT, int R, int WT, int XB, int NRM, bool MOE = false>
 __device__ __forceinline__ void qmm_body(const QmmArgs& a, const QmmPairOff po = QmmPairOff{0, 0, 0, 0, 0}) {
-    qmm_stamp(a, 0);
     QMM_TL_DECL;
     QMM_TL(0);
     qmm_kernarg_burst(a);
     QMM_TL(1);
-    // probe modes of this kernel exist only in -DMI355_QMM_PROBES builds (tools/): every guarded load or branch in the hot
-    // loop costs the production kernel measurable time
-    const int dbg = QMM_DBG(a);
     constexpr int NV = BT < 4 ? BT : 4;
     constexpr int PF = (R > QMM_PF_MIN) ? R : QMM_PF_MIN;
     constexpr int PFK = PF / R;                                  // ring depth in k-blocks
@@ -851,31 +830,23 @@ __device__ __forceinline__ void qmm_body(const QmmArgs& a, const QmmPairOff po =
         for (int q = 0; q < PFK; ++q) {
             const int kbi = kbi0 + q;
             const bool active = kbi < n_my_kb;                    // wave-uniform
-            if (active && (dbg < 3 || dbg == 7)) stage_kblock3<BT, XB, NRM>(a, xr[q], ximg, lane, ss);
+            if (active) stage_kblock3<BT, XB, NRM>(a, xr[q], ximg, lane, ss);
             QMM_TL_ONCE(3);
             const int kbn = wave + NW * (kbi + PFK);
-            if (dbg < 3 || dbg == 7) xr[q] = load_x<BT, XB, NRM>(a, kbn <= kb_last ? kbn : kb_last, lane, nwp, MOE ? po.x_bytes : 0);
+            xr[q] = load_x<BT, XB, NRM>(a, kbn <= kb_last ? kbn : kb_last, lane, nwp, MOE ? po.x_bytes : 0);
             const bool ok = kbi + PFK < n_my_kb;
             if constexpr (WT != 0) {
                 // every tile of the launch has one type: the R tiles of this k-block share C_in and the A fragments
                 if (active) {
-                    if (dbg >= 1 && dbg != 7) {
+                    // at most two tiles share C_in / the A fragments: four at once cost 248 VGPRs (2 waves/SIMD)
+                    constexpr int RJ = (R < 2 || (R > 2 && WT == MI355_GGML_Q6_K)) ? 1 : 2;   // Q6_K x 4 tiles (lm_head): one at a time keeps 3 waves/SIMD
 #pragma unroll
-                        for (int r = 0; r < R; ++r) {
-                            const TileRegs& t = buf[q * R + r];
-                            y[r][0] += __uint_as_float((t.a.x ^ t.b.x ^ t.c.x ^ t.d.x ^ t.b.w ^ t.c.w) & 0x3FFFFFu);
-                        }
-                    } else {
-                        // at most two tiles share C_in / the A fragments: four at once cost 248 VGPRs (2 waves/SIMD)
-                        constexpr int RJ = (R < 2 || (R > 2 && WT == MI355_GGML_Q6_K)) ? 1 : 2;   // Q6_K x 4 tiles (lm_head): one at a time keeps 3 waves/SIMD
-#pragma unroll
-                        for (int r0 = 0; r0 < R; r0 += RJ) {
-                            if (WT == MI355_GGML_Q4_K) compute3_q4k<BT, NV, RJ>(&buf[q * R + r0], ximg, lane, y + r0);
-                            else compute3_q6k<BT, NV, RJ>(&buf[q * R + r0], ximg, lane, y + r0);
+                    for (int r0 = 0; r0 < R; r0 += RJ) {
+                        if (WT == MI355_GGML_Q4_K) compute3_q4k<BT, NV, RJ>(&buf[q * R + r0], ximg, lane, y + r0);
+                        else compute3_q6k<BT, NV, RJ>(&buf[q * R + r0], ximg, lane, y + r0);
 #ifdef MI355_QMM_TIMELINE
-                            if (qtl[4] == 0) { asm volatile("" ::"v"(y[r0][0])); qtl[4] = wall_clock64(); }
+                        if (qtl[4] == 0) { asm volatile("" ::"v"(y[r0][0])); qtl[4] = wall_clock64(); }
 #endif
-                        }
                     }
                 }
 #pragma unroll
@@ -886,9 +857,7 @@ __device__ __forceinline__ void qmm_body(const QmmArgs& a, const QmmPairOff po =
                 for (int r = 0; r < R; ++r) {
                     const int s = q * R + r;
                     if (active) {
-                        if (dbg >= 1 && dbg != 7) {
-                            y[r][0] += __uint_as_float((buf[s].a.x ^ buf[s].b.x ^ buf[s].c.x ^ buf[s].d.x ^ buf[s].b.w ^ buf[s].c.w) & 0x3FFFFFu);
-                        } else if (wtype[r] == MI355_GGML_Q4_K) {
+                        if (wtype[r] == MI355_GGML_Q4_K) {
                             compute3_q4k<BT, NV, 1>(&buf[s], ximg, lane, &y[r]);
                         } else {
                             compute3_q6k<BT, NV, 1>(&buf[s], ximg, lane, &y[r]);
@@ -903,14 +872,6 @@ __device__ __forceinline__ void qmm_body(const QmmArgs& a, const QmmPairOff po =
         }
     }
 
-    if (dbg == 4) {                                              // probe: weight stream only, no reduction / epilogue
-        float t = 0.f;
-#pragma unroll
-        for (int r = 0; r < R; ++r) t += y[r][0];
-        if (t == 1.2345e-30f) a.out[0] = t;
-        return;
-    }
-    qmm_stamp(a, 1);
     QMM_TL(5);
 #if QMM_LATE_AFTER_LOOP
     // cos / sin of the RoPE lanes are requested HERE, behind the k-block loop (round 6): asked for in the prologue they made the wave that holds
@@ -936,11 +897,9 @@ __device__ __forceinline__ void qmm_body(const QmmArgs& a, const QmmPairOff po =
         }
     }
     __syncthreads();
-    qmm_stamp(a, 2);
     QMM_TL(6);
 
     qmm_epilogue<BT, R>(a, red, red_ss, NW, segi, tile, ep, MOE ? po.out : 0);
-    qmm_stamp(a, 3);
     QMM_TL(7);
     QMM_TL_FLUSH();
 }
@@ -948,9 +907,6 @@ __device__ __forceinline__ void qmm_body(const QmmArgs& a, const QmmPairOff po =
 template <int BT, int R, int WT, int XB, int NRM>
 __global__ void __launch_bounds__(512) qmm_kernel(const QmmArgs a) { qmm_body<BT, R, WT, XB, NRM>(a); }
 #include "qmm_exact.inc"   // parity mode (tests only): exact single-token mat-vecs behind the same fused epilogue
-#ifdef MI355_QMM_PROBES   // probe builds only (tools/build_probe_lib.sh): the Q8_K-activation experiment (round 2)
-#include "probes/qmm_q8.inc"
-#endif
 
 // MoE variant (decode-shaped, BT = 1): blockIdx.y = (token, slot) pair.  The adjusted descriptor is a private copy
 // -- kept out of the dense kernel, where the kernel arguments must stay scalar loads from the kernarg segment.
@@ -1267,7 +1223,7 @@ __device__ __forceinline__ void qmm_gemm_body(const QmmArgs& a, const uint8_t* _
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
         for (int kb = kb_lo; kb < kb_hi; ++kb) {
-            if (kb + 1 < kb_hi && QMM_DBG(a) != 2) dma_kb(kb + 1, (kb + 1) & 1);
+            if (kb + 1 < kb_hi) dma_kb(kb + 1, (kb + 1) & 1);
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __syncthreads();
         }
@@ -1294,8 +1250,7 @@ __device__ __forceinline__ void qmm_gemm_body(const QmmArgs& a, const uint8_t* _
         const bool more = kb + 1 < kb_hi;
         // the next tile streams in while this one is unpacked and multiplied (counted vmcnt: no DMA in this wave)
         TileRegs nxt = load_tile<WT>(wtype, more ? wbase + (size_t)(kb + 1) * wtb : wbase, more ? lane : 0);
-        if (QMM_DBG(a) == 1) { y[0][0][0] += __uint_as_float(cur.a.x ^ cur.b.y ^ cur.c.z); }
-        else if (wtype == MI355_GGML_Q4_K) wide_q4k2<MT>(cur, Lc, lane, y[0]);
+        if (wtype == MI355_GGML_Q4_K) wide_q4k2<MT>(cur, Lc, lane, y[0]);
         else wide_q6k<MT>(cur, Lc, lane, y[0]);
         cur = nxt;
         __syncthreads();                                              // everyone is done with Lc; the loader filled the other buffer
@@ -1321,14 +1276,6 @@ template <int MT, int WT>
 __global__ void __launch_bounds__(512, 4) qmm_gemm_kernel(const QmmArgs a, const uint8_t* __restrict__ img, float* __restrict__ part,
                                                           const int ldp, const int n_slots, const int slot_base) {
     qmm_gemm_body<MT, WT>(a, img, part, ldp, 0, a.nseg, n_slots, slot_base, (int)blockIdx.x);
-}
-// 15 consumers + the loader: twice the waves on one shared image per CU (the image DMA is 2.4x the weight bytes, so a
-// second workgroup per CU is not the way to more waves).  Measured +7 % on gate/up only; kept as a tuning option.
-#define QMG_NC_WIDE 15
-template <int MT, int WT>
-__global__ void __launch_bounds__(1024) qmm_gemm16_kernel(const QmmArgs a, const uint8_t* __restrict__ img, float* __restrict__ part,
-                                                          const int ldp, const int n_slots, const int slot_base) {
-    qmm_gemm_body<MT, WT, QMG_NC_WIDE>(a, img, part, ldp, 0, a.nseg, n_slots, slot_base, (int)blockIdx.x);
 }
 // two runs of segments in ONE launch (q, k in Q4_K + v in Q6_K: the v run alone is 10 workgroups x 13 us): the first nwg0
 // workgroups take run 0 with the WTA body, the rest run 1 with the WTB body -- a uniform branch between two specialised
@@ -1534,18 +1481,14 @@ static QmgStream& qmg_stream(hipStream_t st) {
 // mi355_internal_moe_stage_grouped builds images only for it, mi355_internal_moe_scatter_combine_to_image stages only for it): three hand
 // copies of this condition had to agree for the fused MoE staging to be correct.  Defined below the tuning switches.
 static bool qmg_wide_one_launch(int B);
-static int g_tune_qmv = 0;                                    // mi355_set_tuning(20, 1): single-token launches take the LDS-DMA engine (qmv_engine.inc) one by one -- measured slower than qmm_kernel per launch (fixed cost), faster chained
-static int g_tune_qmv_nc = 8;                                 // mi355_set_tuning(21, n): consumer waves per workgroup of the engine (1..15)
 static int g_tune_exact_act = 0;                              // mi355_set_tuning(24, 1): "exact" activations on the 9..32-token and prompt paths: f16 hi + lo planes (22 bits) instead of one f16 plane
-static int g_tune_chain_b1 = 0;                               // mi355_set_tuning(23, 1): probe builds: chain the single-token mat-vecs between two attention calls into one persistent launch
-static int g_tune_qmv_ring = 0;                               // mi355_set_tuning(22, 64): the engine never takes the 128 KiB ring (A/B)
 static int g_tune_chain = 1;                                  // mi355_set_tuning(9, 0): never chain (A/B experiments)
-static int g_tune_wide16 = 0;                                 // mi355_set_tuning(15, n): launches of >= n (row tile x k-block) units use 16-wave workgroups
-static int g_tune_merge = 1;                                  // mi355_set_tuning(14, 0): one launch per run of same-type segments (A/B)
-static int g_tune_ks_minkb = 2;                               // mi355_set_tuning(17, n): fewest k-blocks a k-split keeps per workgroup
-static int g_tune_grp_ks_target = 4096;                       // mi355_set_tuning(16, n): the same for grouped launches (slots of all groups)
-static int g_tune_ks_target = 1024;                           // mi355_set_tuning(10, n): split K until a launch has n row-tile x k-split slots
-static int g_tune_wide_fuse = 0;                              // mi355_set_tuning(49, 1), probe builds only: EXPERIMENT, the 9..32-token path runs its split-K epilogue inside the GEMM launches (lost its A/B: qmm_wide1_gemm.inc)
+// k-split of the 9..32-token launches: split K until a launch has QMG_KS_TARGET (row tile, k-split) slots = 4 consumer waves per CU,
+// keeping >= QMG_KS_MINKB k-blocks per workgroup.  (Measured at batch 32: targets 512 / 768 / 1024 / 1280 / 1536 / 2048 / 4096 ->
+// 4081 / 4634 / 4835-4900 / 4737 / 4742 / 4686 / 4607 tok/s: less splitting = fewer partial sums for the epilogue and longer pipelines.)
+#define QMG_KS_TARGET 1024
+#define QMG_KS_MINKB 2
+#define QMG_GRP_KS_TARGET 4096                                // the same for grouped launches (slots of all groups)
 static inline int qmg_buf(void** p, int key, size_t need, hipStream_t st) { return mi355_scratch_get(p, key, need, st, false); }
 
 template <int MT>
@@ -1557,15 +1500,8 @@ static int qmg_launch(const QmmArgs& a0, hipStream_t st) {
     for (int s = 0; s < a.nseg; ++s) n_slots += a.seg[s].n_tiles;
     const int ldp = n_slots * 16;
     const size_t kbb = qmg_kb_bytes(MT);
-    // split K until the launch has >= 1024 (row tile, k-split) slots = 4 consumer waves per CU, keeping >= 2 k-blocks per
-    // workgroup.  (Measured at batch 32: targets 512 / 768 / 1024 / 1280 / 1536 / 2048 / 4096 -> 4081 / 4634 / 4835-4900 /
-    // 4737 / 4742 / 4686 / 4607 tok/s: less splitting = fewer partial sums for the epilogue and longer pipelines.)
-    const bool wide16 = g_tune_wide16 > 0 && (int64_t)n_slots * nkb >= g_tune_wide16;
-    const int NCq = wide16 ? QMG_NC_WIDE : QMG_NC;
     int ks = 1;
-    if (wide16) { while ((n_slots + NCq - 1) / NCq * ks < 200 && nkb / (ks * 2) >= 4) ks *= 2; }
-    else if (g_tune_ks_target > 0) { while (n_slots * ks < g_tune_ks_target && nkb / (ks * 2) >= g_tune_ks_minkb) ks *= 2; }
-    else { while ((n_slots + QMG_NC - 1) / QMG_NC * ks < -g_tune_ks_target && nkb / (ks * 2) >= g_tune_ks_minkb) ks *= 2; }
+    while (n_slots * ks < QMG_KS_TARGET && nkb / (ks * 2) >= QMG_KS_MINKB) ks *= 2;
     // activation image: staged by the previous launch's epilogue (chain) or by the prep kernel now
     QmgStream& qs = qmg_stream(st);
     const bool chained = qs.chain.valid && qs.chain.x == a.x && qs.chain.B == a.B && qs.chain.K == a.K &&
@@ -1587,8 +1523,6 @@ static int qmg_launch(const QmmArgs& a0, hipStream_t st) {
         (void)hipFuncSetAttribute((const void*)qmm_gemm_kernel<MT, MI355_GGML_Q4_K>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         (void)hipFuncSetAttribute((const void*)qmm_gemm_kernel<MT, MI355_GGML_Q6_K>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         (void)hipFuncSetAttribute((const void*)qmm_gemm2_kernel<MT, MI355_GGML_Q4_K, MI355_GGML_Q6_K>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)qmm_gemm16_kernel<MT, MI355_GGML_Q4_K>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)qmm_gemm16_kernel<MT, MI355_GGML_Q6_K>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         attr_done.set();
     }
     uint8_t* img = static_cast<uint8_t*>(imgp);
@@ -1598,7 +1532,7 @@ static int qmg_launch(const QmmArgs& a0, hipStream_t st) {
     // spill (the mixed build did); each run writes its own columns of the partial-sum buffer
     int s_split = 0, slots0 = 0;                                     // exactly one Q4_K run followed by one Q6_K run: one launch
     while (s_split < a.nseg && a.seg[s_split].type == MI355_GGML_Q4_K) slots0 += a.seg[s_split++].n_tiles;
-    bool two_runs = g_tune_merge && !wide16 && s_split > 0 && s_split < a.nseg;
+    bool two_runs = s_split > 0 && s_split < a.nseg;
     for (int q = s_split; q < a.nseg; ++q) two_runs = two_runs && a.seg[q].type == MI355_GGML_Q6_K;
     if (two_runs) {
         const int slots1 = n_slots - slots0;
@@ -1612,12 +1546,8 @@ static int qmg_launch(const QmmArgs& a0, hipStream_t st) {
         r.nseg = s1 - s0;
         int run_slots = 0;
         for (int q = 0; q < r.nseg; ++q) { r.seg[q] = a.seg[s0 + q]; run_slots += r.seg[q].n_tiles; }
-        const dim3 ggrid((run_slots + NCq - 1) / NCq, ks);
-        if (wide16 && r.seg[0].type == MI355_GGML_Q4_K)
-            hipLaunchKernelGGL((qmm_gemm16_kernel<MT, MI355_GGML_Q4_K>), ggrid, dim3(1024), 2 * kbb, st, r, img, part, ldp, run_slots, slot_base);
-        else if (wide16)
-            hipLaunchKernelGGL((qmm_gemm16_kernel<MT, MI355_GGML_Q6_K>), ggrid, dim3(1024), 2 * kbb, st, r, img, part, ldp, run_slots, slot_base);
-        else if (r.seg[0].type == MI355_GGML_Q4_K)
+        const dim3 ggrid((run_slots + QMG_NC - 1) / QMG_NC, ks);
+        if (r.seg[0].type == MI355_GGML_Q4_K)
             hipLaunchKernelGGL((qmm_gemm_kernel<MT, MI355_GGML_Q4_K>), ggrid, dim3(512), 2 * kbb, st, r, img, part, ldp, run_slots, slot_base);
         else
             hipLaunchKernelGGL((qmm_gemm_kernel<MT, MI355_GGML_Q6_K>), ggrid, dim3(512), 2 * kbb, st, r, img, part, ldp, run_slots, slot_base);
@@ -1657,22 +1587,12 @@ static int qw1_launch(const QmmArgs& a0, hipStream_t st) {
     // grouped launch: G mat-muls of these shapes in the z extent of every launch (the experts of a mixture-of-experts layer)
     const int G = a.grp_n > 1 ? a.grp_n : 1;
     int ks = 1;
-    if (G > 1) { while ((int64_t)n_slots * G * ks < g_tune_grp_ks_target && nkb / (ks * 2) >= g_tune_ks_minkb) ks *= 2; }
-    else if (g_tune_ks_target > 0) { while (n_slots * ks < g_tune_ks_target && nkb / (ks * 2) >= g_tune_ks_minkb) ks *= 2; }
-    else {
-        // workgroup target: the smallest split (any integer, not only powers of two) that puts >= |target| workgroups on the chip while
-        // every split keeps >= minkb k-blocks; e.g. the 256-tile down projection: 37 workgroups x 7 splits of 8 k-blocks = 259
-        const int n_wg = (n_slots + QMG_NC - 1) / QMG_NC;
-        int want = (-g_tune_ks_target + n_wg - 1) / n_wg;
-        const int ks_max = nkb / g_tune_ks_minkb > 1 ? nkb / g_tune_ks_minkb : 1;
-        if (want > ks_max) want = ks_max;
-        if (want < 1) want = 1;
-        ks = want;
-    }
+    if (G > 1) { while ((int64_t)n_slots * G * ks < QMG_GRP_KS_TARGET && nkb / (ks * 2) >= QMG_KS_MINKB) ks *= 2; }
+    else { while (n_slots * ks < QMG_KS_TARGET && nkb / (ks * 2) >= QMG_KS_MINKB) ks *= 2; }
 #ifndef QW1_Q6K_LONGK_WGS
 #define QW1_Q6K_LONGK_WGS 0
 #endif
-    if (QW1_Q6K_LONGK_WGS > 0 && G == 1 && g_tune_ks_target > 0 && a.nseg == 1 && nkb >= 32 && a.seg[0].type == MI355_GGML_Q6_K) {
+    if (QW1_Q6K_LONGK_WGS > 0 && G == 1 && a.nseg == 1 && nkb >= 32 && a.seg[0].type == MI355_GGML_Q6_K) {
         // Rounds 4-5 (two MFMA chains per Q6_K weight, 411 VALU per tile and k-block: profiles/r03_pmc_sq_b32_set1.json): the long-K Q6_K
         // launch (the down projection: 256 tiles x 56 k-blocks) was bound by its unpack arithmetic, and 37 x 14 = 518 workgroups -- two per
         // CU, the second one's waves in the first's stalls -- beat the power-of-two split (37 x 4): 27.6 -> 23.8 us.  With ONE operand per
@@ -1742,63 +1662,18 @@ static int qw1_launch(const QmmArgs& a0, hipStream_t st) {
         ch = QmgChainOut{oimg, reinterpret_cast<float*>(oimg + kbb * nkb2), a.next_norm_w, a.next_k, MT, kbb, 1};
     }
     const QwGroup grp{a.grp_x, a.grp_out, (int64_t)imgb, (int64_t)ks * BP * ldp, (int64_t)imgb2};
-    // the split-K epilogue inside the GEMM launches (qmm_wide1_gemm.inc): tickets per 256-column block of the output
-    QwFuse fz{};
-    fz.ticket = nullptr; fz.ssp = ssp; fz.ch = ch; fz.ks = ks; fz.n_runs = 0;
-    if (QW1_FUSE_BUILD && g_tune_wide_fuse && G == 1) {
-        void* tk = nullptr;
-        rc = mi355_scratch_get(&tk, MI355_SCR_QMM_TICKET, 8192 * sizeof(unsigned), st, true);
-        if (rc) return rc;
-        if ((ldp + 255) / 256 <= 8192) fz.ticket = static_cast<unsigned*>(tk);
-    }
+    const QwFuse fz{};                                                // unread kernel argument (qmm_wide1_gemm.inc)
     if (!chained && G > 1) hipLaunchKernelGGL((qw1_prep_grp_kernel<MT>), dim3(nkb, MT * 2, G), dim3(256), 0, st, img, ssp, a, kbb, grp);
     else if (!chained) hipLaunchKernelGGL((qw1_prep_kernel<MT>), dim3(nkb, MT * 2), dim3(256), 0, st, img, ssp, a, kbb);
-    // per-tile epilogue inside the GEMM launches (qmm_wide1_gemm.inc, TEPI): mat-muls that stage no image for a successor -- q|k|v (RoPE +
-    // cache write), the lm_head, unchained stores / residual adds.
-    // EXPERIMENT, probe builds only (key 49 = 2): measured in round 4 and lost -- q|k|v 40.7 us against 12.7 + 7.5 us for GEMM + epilogue
-    // launch, the lm_head 158 against 125 + 10 us, the ragged batch-32 step 5336 against 6130 tok/s (profiles/r04_b32_tile_epilogue_ab.txt):
-    // a wave that applies RoPE + the cache write to its eight elements walks eight chains of dependent loads (position -> cos / sin ->
-    // slot -> store) one after the other, where the epilogue launch gives every element its own thread.
-    bool tepi = false;
-#if QW1_FUSE_BUILD
-    tepi = G == 1 && g_tune_wide_fuse == 2 && !fz.ticket && !want && n_slots <= 8192 &&
-           (a.epi == MI355_EPI_QKV_ROPE_CACHE || a.epi == MI355_EPI_STORE || a.epi == MI355_EPI_RESID);
-    if (tepi) {
-        void* tk = nullptr;
-        rc = mi355_scratch_get(&tk, MI355_SCR_QMM_TICKET, 8192 * sizeof(unsigned), st, true);
-        if (rc) return rc;
-        fz.tile_ticket = static_cast<unsigned*>(tk);
-        static bool tepi_attr = false;
-        if (!tepi_attr) {
-            (void)hipFuncSetAttribute((const void*)qw1_gemm_tepi_kernel<MT, MI355_GGML_Q4_K>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            (void)hipFuncSetAttribute((const void*)qw1_gemm_tepi_kernel<MT, MI355_GGML_Q6_K>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            (void)hipFuncSetAttribute((const void*)qw1_gemm2_tepi_kernel<MT, MI355_GGML_Q4_K, MI355_GGML_Q6_K>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            tepi_attr = true;
-        }
-    }
-#endif
     int s_split = 0, slots0 = 0;                                     // exactly one Q4_K run followed by one Q6_K run: one launch
     while (s_split < a.nseg && a.seg[s_split].type == MI355_GGML_Q4_K) slots0 += a.seg[s_split++].n_tiles;
-    bool two_runs = g_tune_merge && s_split > 0 && s_split < a.nseg;
+    bool two_runs = s_split > 0 && s_split < a.nseg;
     for (int q = s_split; q < a.nseg; ++q) two_runs = two_runs && a.seg[q].type == MI355_GGML_Q6_K;
-    // the runs of same-type segments = the launches (or launch halves): every workgroup needs all of them to count a block's arrivals
-    for (int s0 = 0, base = 0; s0 < a.nseg;) {
-        int s1 = s0 + 1, rs = a.seg[s0].n_tiles;
-        while (s1 < a.nseg && a.seg[s1].type == a.seg[s0].type) rs += a.seg[s1++].n_tiles;
-        fz.run_lo[fz.n_runs] = base; fz.run_hi[fz.n_runs] = base + rs; ++fz.n_runs;
-        base += rs;
-        s0 = s1;
-    }
     if (two_runs) {
         const int slots1 = n_slots - slots0;
         const dim3 ggrid((slots0 + QMG_NC - 1) / QMG_NC + (slots1 + QMG_NC - 1) / QMG_NC, ks, G);
         if (G > 1) hipLaunchKernelGGL((qw1_gemm2_grp_kernel<MT, MI355_GGML_Q4_K, MI355_GGML_Q6_K>), ggrid, dim3(512), QW1_NB * kbb, st, a, img, part, ldp, s_split, slots0, slots1, fz, grp);
-        else
-#if QW1_FUSE_BUILD
-        if (tepi) hipLaunchKernelGGL((qw1_gemm2_tepi_kernel<MT, MI355_GGML_Q4_K, MI355_GGML_Q6_K>), ggrid, dim3(512), QW1_NB * kbb + 256, st, a, img, part, ldp, s_split, slots0, slots1, fz);
-        else
-#endif
-        hipLaunchKernelGGL((qw1_gemm2_kernel<MT, MI355_GGML_Q4_K, MI355_GGML_Q6_K>), ggrid, dim3(512), QW1_NB * kbb, st, a, img, part, ldp, s_split, slots0, slots1, fz);
+        else hipLaunchKernelGGL((qw1_gemm2_kernel<MT, MI355_GGML_Q4_K, MI355_GGML_Q6_K>), ggrid, dim3(512), QW1_NB * kbb, st, a, img, part, ldp, s_split, slots0, slots1, fz);
     }
     for (int s0 = 0, slot_base = 0; s0 < a.nseg && !two_runs;) {
         int s1 = s0 + 1;
@@ -1807,33 +1682,13 @@ static int qw1_launch(const QmmArgs& a0, hipStream_t st) {
         r.nseg = s1 - s0;
         int run_slots = 0;
         for (int q = 0; q < r.nseg; ++q) { r.seg[q] = a.seg[s0 + q]; r.moe_stride[q] = a.moe_stride[s0 + q]; run_slots += r.seg[q].n_tiles; }
-        // (the in-launch epilogue walks ALL segments of the mat-mul: it gets the whole descriptor, the GEMM part its own run)
         const dim3 ggrid((run_slots + QMG_NC - 1) / QMG_NC, ks, G);
         if (G > 1) {
             if (r.seg[0].type == MI355_GGML_Q4_K)
                 hipLaunchKernelGGL((qw1_gemm_grp_kernel<MT, MI355_GGML_Q4_K>), ggrid, dim3(512), QW1_NB * kbb, st, r, img, part, ldp, run_slots, slot_base, fz, grp);
             else
                 hipLaunchKernelGGL((qw1_gemm_grp_kernel<MT, MI355_GGML_Q6_K>), ggrid, dim3(512), QW1_NB * kbb, st, r, img, part, ldp, run_slots, slot_base, fz, grp);
-        } else
-#if QW1_FUSE_BUILD
-        if (fz.ticket && r.nseg != a.nseg) {
-            // a mat-mul of several launches: the kernel's segment walk starts at the run's first segment
-            QmmArgs full = a;
-            if (r.seg[0].type == MI355_GGML_Q4_K)
-                hipLaunchKernelGGL((qw1_gemm_run_kernel<MT, MI355_GGML_Q4_K>), ggrid, dim3(512), QW1_NB * kbb, st, full, img, part, ldp, run_slots, slot_base, s0, s1, fz);
-            else
-                hipLaunchKernelGGL((qw1_gemm_run_kernel<MT, MI355_GGML_Q6_K>), ggrid, dim3(512), QW1_NB * kbb, st, full, img, part, ldp, run_slots, slot_base, s0, s1, fz);
-        } else
-#endif
-#if QW1_FUSE_BUILD
-        if (tepi) {                                                   // the whole descriptor: the epilogue needs every segment's rows
-            if (r.seg[0].type == MI355_GGML_Q4_K)
-                hipLaunchKernelGGL((qw1_gemm_tepi_kernel<MT, MI355_GGML_Q4_K>), ggrid, dim3(512), QW1_NB * kbb + 256, st, a, img, part, ldp, run_slots, slot_base, s0, s1, fz);
-            else
-                hipLaunchKernelGGL((qw1_gemm_tepi_kernel<MT, MI355_GGML_Q6_K>), ggrid, dim3(512), QW1_NB * kbb + 256, st, a, img, part, ldp, run_slots, slot_base, s0, s1, fz);
-        } else
-#endif
-        if (r.seg[0].type == MI355_GGML_Q4_K)
+        } else if (r.seg[0].type == MI355_GGML_Q4_K)
             hipLaunchKernelGGL((qw1_gemm_kernel<MT, MI355_GGML_Q4_K>), ggrid, dim3(512), QW1_NB * kbb, st, r, img, part, ldp, run_slots, slot_base, fz);
         else
             hipLaunchKernelGGL((qw1_gemm_kernel<MT, MI355_GGML_Q6_K>), ggrid, dim3(512), QW1_NB * kbb, st, r, img, part, ldp, run_slots, slot_base, fz);
@@ -1844,7 +1699,7 @@ static int qw1_launch(const QmmArgs& a0, hipStream_t st) {
     qs.cur = cur;
     if (G > 1)
         hipLaunchKernelGGL(qmm_epilogue_grp_kernel, dim3((ldp + 255) / 256, want ? BP : a.B, G), dim3(256), 0, st, a, part, ldp, ks, BP, ssp, ch, grp);
-    else if (!fz.ticket && !tepi)
+    else
         hipLaunchKernelGGL(qmm_epilogue_kernel, dim3((ldp + 255) / 256, want ? BP : a.B), dim3(256), 0, st, a, part, ldp, ks, BP, ssp, ch);
     return (int)hipGetLastError();
 }
@@ -1941,35 +1796,16 @@ extern "C" int mi355_internal_pa_stream_reduce_to_image(void* out, const float* 
 }
 
 // ================================================================================================
-// Prompt-step path (num_tokens >= QMP_MIN_TOKENS): the matmul is compute-bound, so it is run as a plain GEMM on the
-// matrix cores instead of streaming the quantised weights once per 32 tokens.
-//   1. `qmp_dequant_kernel`  : repacked Q4_K / Q6_K tiles -> bf16 hi + bf16 lo, row-major [N, K] (w = hi + lo to 2^-17)
-//   2. `qmp_xsplit_kernel`   : activations (RMSNorm applied here) -> bf16 hi + lo, row-major [T, K]
-//   3. three library GEMMs (rocBLAS, bf16 inputs, f32 accumulate): hi.hi + hi.lo + lo.hi  -> f32 [T, N]
-//      (candle's own GPU path dequantises to f16 and calls the vendor GEMM for prompts [EXT]; the hi/lo split keeps
-//       the result at f32-activation accuracy so the same 1e-3 logit bound holds as for decode)
-//   4. `qmm_epilogue_kernel` : the same fused epilogues (bias / residual / SiLU*mul / RoPE + cache scatter)
-// rocBLAS is bound with dlopen (the copy torch already loaded if there is one), like RCCL in host_model.cpp.
-#include <dlfcn.h>
-#define QMP_MIN_TOKENS 96
+// Prompt-step path (num_tokens >= QMP_MIN_TOKENS): the matmul is compute-bound, so it is run as a GEMM on the matrix cores
+// (qmm_prefill.inc) instead of streaming the quantised weights once per 32 tokens.
+#define QMP_MIN_TOKENS 96                                  // fewest tokens that take the prompt-step GEMM
 
-#ifdef MI355_QMM_PROBES   // probe builds only (tools/build_probe_lib.sh): first-generation prompt path: weight image for library GEMMs
-#include "probes/qmp_kernels.inc"
-#endif
-
-#ifdef MI355_QMM_PROBES   // probe builds only (tools/build_probe_lib.sh): rocBLAS by dlopen (A/B partner of the hand-written prompt GEMMs)
-#include "probes/qmp_rocblas.inc"
-#endif
-
-static int g_tune_qpg = 2;                                 // mi355_set_tuning(11, v): prompt-step GEMM workgroup tile: 2 (default since round 4) = 64 tokens x 256 rows, 0 = 32 x 512 (rounds 2-3), 1 / 3: A/B variants
 static int g_tune_qpg_fepi = 1;                            // mi355_set_tuning(48, 0): A/B, separate epilogue launch.  Default: the prompt-step GEMM applies the epilogue itself (Q4_K launches; store / residual / SiLU * up; round 4: +7 % on the prompt step)
-static int g_tune_qpg_min = 96;                            // mi355_set_tuning(12, n): fewest tokens that take the prompt-step GEMM (QMP_MIN_TOKENS)
-static int g_tune_dbg = 0;                                 // mi355_set_tuning(2, v): probe / ablation modes (experiments only)
 
 #include "qmm_prefill.inc"
 
 // hand-written prompt-step GEMM (qmm_prefill.inc); returns hipErrorNotSupported for launches it does not cover (then the
-// caller keeps the library-GEMM path)
+// caller streams the weights 32 tokens at a time)
 static int qpg_launch(const QmmArgs& a0, hipStream_t st) {
     QmmArgs a = a0;
     a.paired = 0;
@@ -1986,7 +1822,6 @@ static int qpg_launch(const QmmArgs& a0, hipStream_t st) {
     void* ws = nullptr;
     int rc = qmg_buf(&ws, MI355_SCR_QMP_WS, xa_b + sf_b + 2 * rs_b + c_b + 4096, st);
     if (rc) return rc;
-    a.dbg = g_tune_dbg;                                     // ablation bits of the prompt-step GEMM (experiments only)
     uint8_t* base = static_cast<uint8_t*>(ws);
     QpgImg im;
     im.xa = base; im.sfrag = base + xa_b;
@@ -1997,16 +1832,7 @@ static int qpg_launch(const QmmArgs& a0, hipStream_t st) {
     float* C = reinterpret_cast<float*>(base + xa_b + sf_b + 2 * rs_b);
     static Mi355DevOnce attr_done;
     if (!attr_done.done()) {
-#define QPG_ATTR(MTW, NTW, WM, WN, DEEP) \
-        (void)hipFuncSetAttribute((const void*)qpg_gemm_kernel<MI355_GGML_Q4_K, MTW, NTW, WM, WN, DEEP, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024); \
-        (void)hipFuncSetAttribute((const void*)qpg_gemm_kernel<MI355_GGML_Q4_K, MTW, NTW, WM, WN, DEEP, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024)
-        QPG_ATTR(4, 2, 1, 8, false);
-#ifdef MI355_QMM_PROBES
-        QPG_ATTR(2, 4, 1, 8, false); QPG_ATTR(4, 4, 1, 8, false); QPG_ATTR(2, 4, 2, 4, false);
-        (void)hipFuncSetAttribute((const void*)qpg_gemm_kernel<MI355_GGML_Q4_K, 2, 4, 1, 8, false, 1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
-        (void)hipFuncSetAttribute((const void*)qpg_gemm_q6k_kernel<1, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
-#endif
-#undef QPG_ATTR
+        (void)hipFuncSetAttribute((const void*)qpg_gemm_kernel<MI355_GGML_Q4_K, 4, 2, 1, 8, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
         (void)hipFuncSetAttribute((const void*)qpg_gemm_lds2_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
         (void)hipFuncSetAttribute((const void*)qpg_gemm_lds2_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
         (void)hipFuncSetAttribute((const void*)qpg_gemm_lds2_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
@@ -2017,35 +1843,27 @@ static int qpg_launch(const QmmArgs& a0, hipStream_t st) {
         (void)hipFuncSetAttribute((const void*)qpg_gemm_q6k_lds_kernel<true, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         attr_done.set();
     }
-    if (a.blk_tab && g_tune_qpg != 2) return (int)hipErrorNotSupported;                   // only the LDS-fed kernel reads a block table
     hipLaunchKernelGGL(qpg_rowprep_kernel, dim3(Tpad), dim3(256), 0, st, a, im);          // row statistics + image, one launch (workgroup = token)
-    // EXPERIMENT (mi355_set_tuning(48, 1)): all segments Q4_K, one activation plane, the default wave tile, and an epilogue that is a
-    // store / residual add / SiLU * up over two equal segments -> the GEMM writes the outputs itself, no C buffer, no epilogue launch
+    // mi355_set_tuning(48, 1), the default: all segments Q4_K, one activation plane, and an epilogue that is a store / residual add /
+    // SiLU * up over two equal segments -> the GEMM writes the outputs itself, no C buffer, no epilogue launch
     {
         bool all_q4 = true;
         for (int s = 0; s < a.nseg; ++s) all_q4 = all_q4 && a.seg[s].type == MI355_GGML_Q4_K;
         const bool epi_ok = a.epi == MI355_EPI_STORE || a.epi == MI355_EPI_RESID ||
                             (a.epi == MI355_EPI_SILU_MUL && a.nseg == 2 && a.seg[0].n_tiles == a.seg[1].n_tiles && a.seg[0].n_rows == a.seg[1].n_rows);
-        if (g_tune_qpg_fepi && all_q4 && epi_ok && parts == 1 && (g_tune_qpg == 0 || g_tune_qpg == 2)) {
+        if (g_tune_qpg_fepi && all_q4 && epi_ok && parts == 1) {
             QmmArgs r = a;
             r.norm_w = nullptr;                                 // applied while the image was built
-            if (g_tune_qpg == 2) {                              // 64 tokens x 256 rows per workgroup (waves 64 x 32), two workgroups per CU
-                const dim3 g_(Tpad / 64, (n_slots + 15) / 16), b_(512);
-                if (a.blk_tab) hipLaunchKernelGGL((qpg_gemm_lds2_kernel<true, true>), g_, b_, (size_t)QPG2_BYTES, st, r, im, C, ldp, n_slots, 0);
-                else hipLaunchKernelGGL((qpg_gemm_lds2_kernel<true>), g_, b_, (size_t)QPG2_BYTES, st, r, im, C, ldp, n_slots, 0);
-            } else {
-#ifdef MI355_QMM_PROBES
-                const dim3 g_(Tpad / 32, (n_slots + 31) / 32), b_(512);   // rounds 2-3: 32 x 512, register-fed
-                const size_t sh_ = (size_t)2 * 32 * QPG_ROWB;
-                hipLaunchKernelGGL((qpg_gemm_kernel<MI355_GGML_Q4_K, 2, 4, 1, 8, false, 1, true>), g_, b_, sh_, st, r, im, C, ldp, n_slots, 0);
-#endif
-            }
+            // 64 tokens x 256 rows per workgroup (waves 64 x 32), two workgroups per CU
+            const dim3 g_(Tpad / 64, (n_slots + 15) / 16), b_(512);
+            if (a.blk_tab) hipLaunchKernelGGL((qpg_gemm_lds2_kernel<true, true>), g_, b_, (size_t)QPG2_BYTES, st, r, im, C, ldp, n_slots, 0);
+            else hipLaunchKernelGGL((qpg_gemm_lds2_kernel<true>), g_, b_, (size_t)QPG2_BYTES, st, r, im, C, ldp, n_slots, 0);
             return (int)hipGetLastError();
         }
         if (a.blk_tab) {
             // block-table launches: Q4_K above; one Q6_K matrix with a store / residual epilogue here (the down projections of a Q4_K_M file)
             if (a.nseg == 1 && a.seg[0].type == MI355_GGML_Q6_K && (a.epi == MI355_EPI_STORE || a.epi == MI355_EPI_RESID) && parts == 1 &&
-                g_tune_qpg == 2 && g_tune_qpg_fepi) {
+                g_tune_qpg_fepi) {
                 QmmArgs r = a;
                 r.norm_w = nullptr;
                 hipLaunchKernelGGL((qpg_gemm_q6k_lds_kernel<true, 2, true>), dim3(Tpad / 64, (n_slots + 15) / 16), dim3(512), (size_t)QPG6_LDS_BYTES, st, r, im, C,
@@ -2068,7 +1886,7 @@ static int qpg_launch(const QmmArgs& a0, hipStream_t st) {
 #define QPG_FUSE_QKV 1          // A/B builds: 0 = q | k | v through the C buffer and the epilogue launch (rounds 2-5)
 #endif
     // (from 1024 tokens: measured +0.7 % at 2048 and +1.2 % at 4096 tokens, -1.9 % at 512 -- profiles/r06_prompt_qkv_fused_ab.txt)
-    if (QPG_FUSE_QKV && T >= 1024 && g_tune_qpg_fepi && parts == 1 && g_tune_qpg == 2 && a.epi == MI355_EPI_QKV_ROPE_CACHE && a.nseg == 3 &&
+    if (QPG_FUSE_QKV && T >= 1024 && g_tune_qpg_fepi && parts == 1 && a.epi == MI355_EPI_QKV_ROPE_CACHE && a.nseg == 3 &&
         a.seg[0].type == MI355_GGML_Q4_K && a.seg[1].type == MI355_GGML_Q4_K && (QPG_FUSE_Q6K || a.seg[2].type == MI355_GGML_Q4_K)) {
         const bool v4 = a.seg[2].type == MI355_GGML_Q4_K;
         QmmArgs r = a;
@@ -2099,30 +1917,14 @@ static int qpg_launch(const QmmArgs& a0, hipStream_t st) {
         int run_slots = 0;
         for (int q = 0; q < r.nseg; ++q) { r.seg[q] = a.seg[s0 + q]; run_slots += r.seg[q].n_tiles; }
         if (r.seg[0].type == MI355_GGML_Q4_K) {
-            // variants (mi355_set_tuning(11, v)): wave tile (m-tiles x row tiles) and wave grid; PARTS = activation planes
-#define QPG_GO(MTW, NTW, WM, WN, DEEP) do { \
-                const dim3 g_(Tpad / (16 * MTW * WM), (run_slots + NTW * WN - 1) / (NTW * WN)), b_(WM * WN * 64); \
-                const size_t sh_ = (size_t)2 * parts * (16 * MTW * WM) * QPG_ROWB; \
-                if (parts == 1) hipLaunchKernelGGL((qpg_gemm_kernel<MI355_GGML_Q4_K, MTW, NTW, WM, WN, DEEP, 1>), g_, b_, sh_, st, r, im, C, ldp, run_slots, slot_base); \
-                else hipLaunchKernelGGL((qpg_gemm_kernel<MI355_GGML_Q4_K, MTW, NTW, WM, WN, DEEP, 2>), g_, b_, sh_, st, r, im, C, ldp, run_slots, slot_base); } while (0)
-            switch (g_tune_qpg) {
-#ifdef MI355_QMM_PROBES
-                case 1: QPG_GO(4, 4, 1, 8, false); break;              //  64 x 512, waves 64 x 64
-                case 3: QPG_GO(2, 4, 2, 4, false); break;              //  64 x 256, waves 32 x 64
-                case 0: QPG_GO(2, 4, 1, 8, false); break;              //  32 x 512, waves 32 x 64: measured best in round 2 (hi + lo planes); with one plane 64 x 256 wins (round 4: 25.7 k -> 27.0 k tok/s at T = 2048)
-#endif
-                default:                                                //  64 x 256, waves 64 x 32, two workgroups per CU; one activation plane: image and weights through LDS by DMA
-                    if (parts == 1) {
-                        const dim3 g4(Tpad / 64, (run_slots + 15) / 16), b_(512);
-                        hipLaunchKernelGGL((qpg_gemm_lds2_kernel<false>), g4, b_, (size_t)QPG2_BYTES, st, r, im, C, ldp, run_slots, slot_base);
-                    } else {
-                        QPG_GO(4, 2, 1, 8, false);                      // hi + lo planes ("exact" activations): the register-fed form
-                    }
-                    break;
-            }
-#undef QPG_GO
+            // 64 x 256, waves 64 x 32, two workgroups per CU
+            const dim3 g4(Tpad / 64, (run_slots + 15) / 16), b_(512);
+            if (parts == 1)                                             // one activation plane: image and weights through LDS by DMA
+                hipLaunchKernelGGL((qpg_gemm_lds2_kernel<false>), g4, b_, (size_t)QPG2_BYTES, st, r, im, C, ldp, run_slots, slot_base);
+            else                                                        // hi + lo planes ("exact" activations): the register-fed form
+                hipLaunchKernelGGL((qpg_gemm_kernel<MI355_GGML_Q4_K, 4, 2, 1, 8, 2>), g4, b_, (size_t)2 * 2 * 64 * QPG_ROWB, st, r, im, C, ldp, run_slots, slot_base);
         } else {
-            if (parts == 1 && g_tune_qpg == 2) {                        // Q6_K: 64 tokens x 256 rows per workgroup; token blocks fastest
+            if (parts == 1) {                      // Q6_K: 64 tokens x 256 rows per workgroup; token blocks fastest
                 const dim3 grid(Tpad / 64, (run_slots + 15) / 16);
                 // the whole mat-mul is this one Q6_K run and its epilogue is a store / residual add: fused store loop, no C buffer, no launch
                 // (from 4096 tokens -- measured: +1.2 % at 4096, -0.2 % at 2048: profiles/r06_prompt_q6k_fused_ab.txt)
@@ -2134,10 +1936,6 @@ static int qpg_launch(const QmmArgs& a0, hipStream_t st) {
                 hipLaunchKernelGGL((qpg_gemm_q6k_lds_kernel<false>), grid, dim3(512), (size_t)QPG6_LDS_BYTES, st, r, im, C, ldp, run_slots, slot_base);
             } else {
                 const dim3 grid(Tpad / 32, (run_slots + 15) / 16);     // 32 tokens x 256 rows, register-fed: hi + lo planes ("exact" activations)
-#ifdef MI355_QMM_PROBES
-                if (parts == 1) hipLaunchKernelGGL((qpg_gemm_q6k_kernel<1, 2>), grid, dim3(512), 8 * 1024, st, r, im, C, ldp, run_slots, slot_base);
-                else
-#endif
                 hipLaunchKernelGGL((qpg_gemm_q6k_kernel<2, 2>), grid, dim3(512), 16 * 1024, st, r, im, C, ldp, run_slots, slot_base);
             }
         }
@@ -2150,9 +1948,6 @@ static int qpg_launch(const QmmArgs& a0, hipStream_t st) {
     return (int)hipGetLastError();
 }
 
-#ifdef MI355_QMM_PROBES   // probe builds only (tools/build_probe_lib.sh): launcher of the first-generation prompt path
-#include "probes/qmp_launch.inc"
-#endif
 
 // ------------------------------------------------------------------------------------------------ launcher
 void mi355_pa_set_fused(int v);
@@ -2161,17 +1956,12 @@ void mi355_pa_set_loop(int v);
 void mi355_dense_set_small(int key, int v);
 extern "C" void mi355_host_set_partition_override(int v);
 extern "C" void mi355_host_set_moe_group(int v);
-extern "C" void mi355_dense_set_tile(int v);
 void mi355_prefill_set_fp8_generic(int v);
 void mi355_prefill_set_lds(int v);
-static int g_tune_actq8 = 0;                               // mi355_set_tuning(18, 1): EXPERIMENT, single-token launches quantise x to Q8_K (reference CPU numerics, O2)
-static int g_tune_nw = 0, g_tune_r = 0;                   // 0 = heuristic; mi355_set_tuning (experiments only)
-static int g_tune_prefill_gemm = 1;                        // 0 = always stream the quantised weights (experiments)
-// ---- A/B switches.  The PRODUCT library honours exactly ten keys (documented in include/mi355_vllm.h; their defaults live in the table
-// below, which is applied through the same setters at load time, so `mi355_get_tuning` always returns the live value of a product key);
-// every other key belongs to probe builds (-DMI355_QMM_PROBES, tools/build_probe_lib.sh) and is ignored by the product library.
-void mi355_prefill_set_fp8_generic(int v);
-void mi355_prefill_set_lds(int v);
+static int g_tune_prefill_gemm = 1;                        // mi355_set_tuning(6, v): 1 = prompt steps take the prompt-step GEMM, 0 = always stream the quantised weights (A/B)
+// ---- A/B switches.  The library honours exactly ten keys (documented in include/mi355_vllm.h; their defaults live in the table
+// below, which is applied through the same setters at load time, so `mi355_get_tuning` always returns the live value of a key);
+// every other key is ignored.
 static int32_t g_tune_shadow[64];
 static bool g_tune_shadow_set[64];
 static const int32_t kProductTuning[][2] = {{3, 1}, {5, 0}, {6, 1}, {9, 1}, {24, 0}, {30, 0}, {41, 1}, {44, 1}, {47, 1}, {48, 1}};
@@ -2190,57 +1980,25 @@ static void tuning_apply(int32_t key, int32_t value) {
     else if (key == 44) mi355_pa_set_loop(value);
     else if (key == 47) { mi355_prefill_set_lds(value & 1); mi355_prefill_set_fp8_generic((value >> 1) & 1); }
     else if (key == 48) g_tune_qpg_fepi = value;
-#ifdef MI355_QMM_PROBES
-    else if (key == 0) g_tune_nw = value;
-    else if (key == 1) g_tune_r = value;
-    else if (key == 2) g_tune_dbg = value;
-    else if (key == 10 && value != 0) g_tune_ks_target = value;     // > 0: (row tile x k-split) slots, < 0: workgroups
-    else if (key == 11) g_tune_qpg = value;
-    else if (key == 12 && value > 0) g_tune_qpg_min = value;
-    else if (key == 14) g_tune_merge = value;
-    else if (key == 15) g_tune_wide16 = value;
-    else if (key == 16 && value > 0) g_tune_grp_ks_target = value;
-    else if (key == 17 && value > 0) g_tune_ks_minkb = value;
-    else if (key == 18) g_tune_actq8 = value;
-    else if (key == 20) g_tune_qmv = value;
-    else if (key == 21 && value > 0) g_tune_qmv_nc = value;
-    else if (key == 22) g_tune_qmv_ring = value;
-    else if (key == 23) g_tune_chain_b1 = value;
-    else if (key >= 33 && key <= 38) mi355_dense_set_small(key, value);
-    else if (key == 42) mi355_dense_set_tile(value);
-    else if (key == 49) g_tune_wide_fuse = value;
-#endif
 }
 namespace {
 struct TuningInit {
     TuningInit() {
         for (const auto& kv : kProductTuning) { tuning_apply(kv[0], kv[1]); g_tune_shadow[kv[0]] = kv[1]; g_tune_shadow_set[kv[0]] = true; }
-#ifdef MI355_QMM_PROBES
-        // probe builds: every key has a live value from the start (the defaults of the variables the setters write; ADVICE r4: a scoped
-        // set / restore of a never-set key used to "restore" 0, which several setters ignore and which switches others off)
-        static const int32_t kProbeDefaults[][2] = {{0, 0}, {1, 0}, {2, 0}, {10, 1024}, {11, 2}, {12, 96}, {14, 1}, {15, 0}, {16, 4096}, {17, 2}, {18, 0},
-                                                    {20, 0}, {21, 8}, {22, 0}, {23, 0}, {33, 0}, {34, 0}, {35, 0}, {36, 96}, {37, 0}, {38, 4},
-                                                    {42, 1}, {49, 0}};
-        for (const auto& kv : kProbeDefaults) { g_tune_shadow[kv[0]] = kv[1]; g_tune_shadow_set[kv[0]] = true; }
-#endif
     }
 } g_tuning_init;
 }
-/* 1 when this build honours `key` (the ten product keys; every key in probe builds) */
+/* 1 when the library honours `key` (the ten product keys) */
 extern "C" int32_t mi355_tuning_supported(int32_t key) {
     if (key < 0 || key >= 64) return 0;
-#ifdef MI355_QMM_PROBES
-    return 1;
-#else
     return tuning_is_product_key(key) ? 1 : 0;
-#endif
 }
 extern "C" int32_t mi355_get_tuning(int32_t key) {
     if (key < 0 || key >= 64 || !g_tune_shadow_set[key]) return INT32_MIN;
     return g_tune_shadow[key];
 }
 extern "C" void mi355_set_tuning(int32_t key, int32_t value) {
-    if (!mi355_tuning_supported(key)) return;                       // product build: a probe key is ignored (and stays "never set")
+    if (!mi355_tuning_supported(key)) return;                       // any other key is ignored (and stays "never set")
     g_tune_shadow[key] = value; g_tune_shadow_set[key] = true;
     tuning_apply(key, value);
 }
@@ -2251,16 +2009,6 @@ static size_t qmm_lds_bytes(int BT, int R, int NW) {
 }
 
 static int g_num_cus = 0;
-
-// The LDS-DMA loader / consumer engine for single-token launches and the chained persistent launch built on it are
-// EXPERIMENTS that lost their A/B on the MI355X ("what was tried for batch 1 in round 3"): they are
-// compiled into probe builds only (tools/build_probe_lib.sh); the product library keeps the entry points as refusals.
-#ifdef MI355_QMM_PROBES
-#include "probes/qmv_engine.inc"
-#else
-static int qmv_launch(const QmmArgs&, int, hipStream_t) { return (int)hipErrorNotSupported; }
-extern "C" int mi355_qmv_error(int32_t* out_host, int32_t) { if (out_host) *out_host = 0; return 0; }
-#endif
 
 // Waves per workgroup: the largest NW in {8,4,2,1} for which every workgroup of the launch is resident at
 // once (no second dispatch round => no tail), judged by the occupancy the runtime reports for this variant.
@@ -2286,7 +2034,7 @@ static int qmm_pick_nw(int n_wg, int nkb) {
 }
 
 template <int BT, int R, int WT>
-static int qmm_launch_btrw(QmmArgs& a, int n_wg, int NW, hipStream_t st) {
+static int qmm_launch_btrw(QmmArgs& a, int n_wg, hipStream_t st) {
     a.kch = 0;
     static Mi355DevOnce attr_done;
     if (!attr_done.done()) {
@@ -2304,8 +2052,8 @@ static int qmm_launch_btrw(QmmArgs& a, int n_wg, int NW, hipStream_t st) {
 #ifndef QMM_NW_PAIRED
 #define QMM_NW_PAIRED 2
 #endif
-    if (NW <= 0 && a.paired && BT == 1 && !a.moe_expert && a.K / 256 >= QMM_NW_PAIRED) NW = QMM_NW_PAIRED;
-    if (NW <= 0) NW = qmm_pick_nw<BT, R, WT>(n_wg * (a.moe_expert ? a.moe_pairs : 1), a.K / 256);
+    const int NW = (QMM_NW_PAIRED > 0 && a.paired && BT == 1 && !a.moe_expert && a.K / 256 >= QMM_NW_PAIRED)
+                       ? QMM_NW_PAIRED : qmm_pick_nw<BT, R, WT>(n_wg * (a.moe_expert ? a.moe_pairs : 1), a.K / 256);
     const size_t shm = qmm_lds_bytes(BT, R, NW);
     if (shm > 160 * 1024) return (int)hipErrorInvalidValue;
     if (a.moe_expert) {
@@ -2328,19 +2076,6 @@ static int qmm_launch_btrw(QmmArgs& a, int n_wg, int NW, hipStream_t st) {
             return (int)hipErrorInvalidValue;
         }
     } else {
-#ifdef MI355_QMM_PROBES
-        if constexpr (BT == 1) {
-            if (g_tune_actq8) {
-                const bool xb8 = a.x_dtype == MI355_DTYPE_BF16, nrm8 = a.norm_w != nullptr;
-#define Q8_GO(XB_, NRM_) do { \
-                    (void)hipFuncSetAttribute((const void*)qmm_q8_kernel<R, WT, XB_, NRM_>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-                    hipLaunchKernelGGL((qmm_q8_kernel<R, WT, XB_, NRM_>), dim3(n_wg), dim3(64 * NW), shm, st, a); } while (0)
-                if (xb8 && nrm8) Q8_GO(1, 1); else if (xb8) Q8_GO(1, 0); else if (nrm8) Q8_GO(0, 1); else Q8_GO(0, 0);
-#undef Q8_GO
-                return (int)hipGetLastError();
-            }
-        }
-#endif
         const bool xb = a.x_dtype == MI355_DTYPE_BF16, nrm = a.norm_w != nullptr;
         if (xb && nrm) hipLaunchKernelGGL((qmm_kernel<BT, R, WT, 1, 1>), dim3(n_wg), dim3(64 * NW), shm, st, a);
         else if (xb) hipLaunchKernelGGL((qmm_kernel<BT, R, WT, 1, 0>), dim3(n_wg), dim3(64 * NW), shm, st, a);
@@ -2351,17 +2086,17 @@ static int qmm_launch_btrw(QmmArgs& a, int n_wg, int NW, hipStream_t st) {
 }
 
 template <int BT, int R>
-static int qmm_launch_btr(QmmArgs& a, int wt, int n_wg, int NW, hipStream_t st) {
-    if (wt == MI355_GGML_Q4_K) return qmm_launch_btrw<BT, R, MI355_GGML_Q4_K>(a, n_wg, NW, st);
-    if (wt == MI355_GGML_Q6_K) return qmm_launch_btrw<BT, R, MI355_GGML_Q6_K>(a, n_wg, NW, st);
-    return qmm_launch_btrw<BT, R, 0>(a, n_wg, NW, st);
+static int qmm_launch_btr(QmmArgs& a, int wt, int n_wg, hipStream_t st) {
+    if (wt == MI355_GGML_Q4_K) return qmm_launch_btrw<BT, R, MI355_GGML_Q4_K>(a, n_wg, st);
+    if (wt == MI355_GGML_Q6_K) return qmm_launch_btrw<BT, R, MI355_GGML_Q6_K>(a, n_wg, st);
+    return qmm_launch_btrw<BT, R, 0>(a, n_wg, st);
 }
 
 template <int BT>
-static int qmm_launch_bt(QmmArgs& a, int R, int wt, int n_wg, int NW, hipStream_t st) {
-    if (R == 4) return qmm_launch_btr<BT, 4>(a, wt, n_wg, NW, st);
-    if (R == 2) return qmm_launch_btr<BT, 2>(a, wt, n_wg, NW, st);
-    return qmm_launch_btr<BT, 1>(a, wt, n_wg, NW, st);
+static int qmm_launch_bt(QmmArgs& a, int R, int wt, int n_wg, hipStream_t st) {
+    if (R == 4) return qmm_launch_btr<BT, 4>(a, wt, n_wg, st);
+    if (R == 2) return qmm_launch_btr<BT, 2>(a, wt, n_wg, st);
+    return qmm_launch_btr<BT, 1>(a, wt, n_wg, st);
 }
 
 // Run one fused quantised mat-mul over batch rows [0,B) in M-tiles of 8 batch entries.
@@ -2459,7 +2194,7 @@ static int qmm_exact_launch(QmmArgs a, hipStream_t st) {
 }
 
 static bool qmg_wide_one_launch(int B) {
-    return B > 8 && B <= 8 * QMW_MAXMT && !g_tune_exact_act && !g_qmm_exact && !(B >= g_tune_qpg_min && g_tune_prefill_gemm);
+    return B > 8 && B <= 8 * QMW_MAXMT && !g_tune_exact_act && !g_qmm_exact && !(B >= QMP_MIN_TOKENS && g_tune_prefill_gemm);
 }
 
 int mi355_qmm_launch(QmmArgs a, int64_t stream) {
@@ -2520,38 +2255,20 @@ int mi355_qmm_launch(QmmArgs a, int64_t stream) {
         for (int s = 0; s < a.nseg; ++s) any_q6 = any_q6 || a.seg[s].type == MI355_GGML_Q6_K;
         if (div4 && total_tiles / 4 >= 1024 && !any_q6) R = 4;
     }
-    if (g_tune_r > 0 && !(a.paired && g_tune_r == 1)) {
-        if (g_tune_r == 4 && (a.paired ? a.seg[0].n_tiles % 2 == 0 : div4)) R = 4;
-        else if (g_tune_r == 2 && (a.paired || div2)) R = 2;
-        else if (g_tune_r == 1 && !a.paired) R = 1;
-    }
     const int n_wg = a.paired ? a.seg[0].n_tiles / (R / 2) : total_tiles / R;
-    const int nkb = a.K / 256;
-    int NW = 0;                                               // 0 = occupancy-aware choice per kernel variant
-    if (g_tune_nw > 0) { NW = g_tune_nw; while (NW > 1 && nkb < NW) NW >>= 1; if (NW > 8) NW = 8; }
     hipStream_t st = to_stream(stream);
     int wt = a.seg[0].type;                                   // uniform tile type of the launch, else 0 (mixed)
     for (int s = 1; s < a.nseg; ++s) if (a.seg[s].type != wt) wt = 0;
-    a.dbg = g_tune_dbg;
     if (a.moe_expert) {                                       // every (token, slot) pair is a 1-token mat-vec of its own expert
         if (a.moe_pairs < 1 || a.moe_xdiv < 1 || a.epi == MI355_EPI_QKV_ROPE_CACHE || a.epi == MI355_EPI_RESID) return (int)hipErrorInvalidValue;
         a.B = 1;
-        return qmm_launch_bt<1>(a, R, wt, n_wg, NW, st);
+        return qmm_launch_bt<1>(a, R, wt, n_wg, st);
     }
-    if (a.blk_tab && !(a.B >= g_tune_qpg_min && g_tune_prefill_gemm == 1)) return (int)hipErrorNotSupported;   // only the prompt GEMM reads a block table
-    if (a.B >= g_tune_qpg_min && g_tune_prefill_gemm) {
-        // prompt step: the hand-written quantised GEMM (qmm_prefill.inc).  mi355_set_tuning(6, 2) = the first-generation path
-        // (bf16 hi/lo weight image + three library GEMMs) for A/B runs; (6, 0) = stream the weights 32 tokens at a time.
-#ifdef MI355_QMM_PROBES
-        if (g_tune_prefill_gemm == 2) {
-            const int rcp = qmp_launch(a, st);
-            if (rcp != (int)hipErrorSharedObjectInitFailed) return rcp;
-        } else
-#endif
-        {
-            const int rcq = qpg_launch(a, st);
-            if (rcq != (int)hipErrorNotSupported || a.blk_tab) return rcq;
-        }
+    if (a.blk_tab && !(a.B >= QMP_MIN_TOKENS && g_tune_prefill_gemm == 1)) return (int)hipErrorNotSupported;   // only the prompt GEMM reads a block table
+    if (a.B >= QMP_MIN_TOKENS && g_tune_prefill_gemm) {
+        // prompt step: the hand-written quantised GEMM (qmm_prefill.inc); mi355_set_tuning(6, 0) = stream the weights 32 tokens at a time
+        const int rcq = qpg_launch(a, st);
+        if (rcq != (int)hipErrorNotSupported || a.blk_tab) return rcq;
     }
     const int B = a.B;
     const size_t xes = (a.x_dtype == MI355_DTYPE_BF16) ? 2 : 4;
@@ -2589,13 +2306,10 @@ int mi355_qmm_launch(QmmArgs a, int64_t stream) {
         a.positions = pos0 ? pos0 + b0 : nullptr;
         a.slot_mapping = slot0 ? slot0 + b0 : nullptr;
         int rc;
-        if (bn == 1) {
-            rc = qmv_launch(a, wt, st);                       // LDS-DMA loader / consumer engine (qmv_engine.inc)
-            if (rc == (int)hipErrorNotSupported) rc = qmm_launch_bt<1>(a, R, wt, n_wg, NW, st);
-        }
-        else if (bn == 2) rc = qmm_launch_bt<2>(a, R, wt, n_wg, NW, st);
-        else if (bn <= 4) rc = qmm_launch_bt<4>(a, R, wt, n_wg, NW, st);
-        else rc = qmm_launch_bt<8>(a, R, wt, n_wg, NW, st);
+        if (bn == 1) rc = qmm_launch_bt<1>(a, R, wt, n_wg, st);
+        else if (bn == 2) rc = qmm_launch_bt<2>(a, R, wt, n_wg, st);
+        else if (bn <= 4) rc = qmm_launch_bt<4>(a, R, wt, n_wg, st);
+        else rc = qmm_launch_bt<8>(a, R, wt, n_wg, st);
         if (rc) return rc;
         b0 += bn;
     }
@@ -2741,10 +2455,3 @@ extern "C" int mi355_qmatmul_fused(const mi355_qmm_desc* d, int64_t stream) {
     if (rc) return rc;
     return mi355_qmm_launch(a, stream);
 }
-
-#ifdef MI355_QMM_PROBES
-#include "probes/qmv_chain.inc"
-#else
-extern "C" int mi355_qmv_chain_sync_bytes(void) { return 256; }
-extern "C" int mi355_qmatmul_chain(const mi355_qmm_desc*, int32_t, void*, int64_t) { return (int)hipErrorNotSupported; }
-#endif

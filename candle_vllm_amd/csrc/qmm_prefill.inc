@@ -201,12 +201,9 @@ __device__ __forceinline__ qpg_h8 qpg_frag_q4k_p(uint32_t w0, uint32_t w0s, uint
 // the kernel is the ACTIVATION operand (measured by ablation: without the image loads the step is 36 % shorter, without the
 // MFMAs or the unpack it is not shorter at all): a wider workgroup tile in N re-reads the image less often, a wider wave
 // tile in N reads each A fragment from LDS less often.
-// XDEEP = activation chunks requested two ahead (a second register set) instead of one.
-// FEPI (EXPERIMENT, mi355_set_tuning(48, 1); not run on hardware yet): the epilogue in the GEMM's own store loop instead of a launch that
-// reads the f32 C [T][ldp] back (10 % of the 2048-token prompt step: r03_prefill_kernel_stats.csv) -- for launches whose segments are all
-// Q4_K and whose epilogue is a store, a residual add or SiLU * up.  SiLU * up: the wave's NTW row tiles are NTW / 2 gate tiles and the
-// SAME tiles of `up`, so gate and up meet in the lane's registers (the slot order of the other modes is untouched).
-template <int WT, int MTW, int NTW, int WM, int WN, bool XDEEP, int PARTS, bool FEPI = false>
+// The register-fed form: since round 4 it runs only for hi + lo activation planes ("exact" activations, PARTS = 2); one plane takes
+// qpg_gemm_lds2_kernel below.
+template <int WT, int MTW, int NTW, int WM, int WN, int PARTS>
 __global__ void __launch_bounds__(WM * WN * 64, 1) qpg_gemm_kernel(const QmmArgs a, const QpgImg im, float* __restrict__ C, const int ldc,
                                                           const int n_slots, const int slot_base) {
     static_assert(WT == MI355_GGML_Q4_K, "Q6_K goes through qpg_gemm_q6k_kernel");
@@ -227,23 +224,14 @@ __global__ void __launch_bounds__(WM * WN * 64, 1) qpg_gemm_kernel(const QmmArgs
     // ---- this wave's four row tiles (slots in the concatenated segment space)
     const uint8_t* wbase[NTW];
     bool have[NTW];
-    int e_sg[NTW], e_tile[NTW];                                      // FEPI: segment and tile of each row tile
-    const bool fsilu = FEPI && a.epi == MI355_EPI_SILU_MUL;
 #pragma unroll
     for (int i = 0; i < NTW; ++i) {
         int slot = bx * SLOTS + wn * NTW + i;
-        if (fsilu) {                                                  // gate tiles pb .. pb + NTW/2 - 1, then the same tiles of `up` (segment 1)
-            const int pb = (bx * WN + wn) * (NTW / 2) + (i % (NTW / 2));
-            slot = (i < NTW / 2) ? pb : a.seg[0].n_tiles + pb;
-            have[i] = pb < a.seg[0].n_tiles;
-        } else {
-            have[i] = slot < n_slots;
-        }
+        have[i] = slot < n_slots;
         if (!have[i]) slot = 0;
         int t = slot, sg = 0;
         while (sg + 1 < a.nseg && t >= a.seg[sg].n_tiles) { t -= a.seg[sg].n_tiles; ++sg; }
         wbase[i] = a.seg[sg].w + (size_t)t * nkb * Q4K_TILE;
-        e_sg[i] = sg; e_tile[i] = t;
     }
     uint4 hdr[NTW], hdrn[NTW], p0[NTW], p1[NTW];
     auto ld_hdr = [&](int kb, uint4 (&H)[NTW]) {
@@ -280,23 +268,18 @@ __global__ void __launch_bounds__(WM * WN * 64, 1) qpg_gemm_kernel(const QmmArgs
     uint32_t Mk = 0x000F000Fu, Ck = 0x64006400u;
     asm volatile("" : "+v"(Mk), "+v"(Ck));
 
-    uint4 xa_[XU], xb_[XU];                                             // activation chunks kc+1 (even kc: xa_) and kc+2 in flight
+    uint4 xa_[XU];                                                      // activation chunk kc+1 in flight
     ld_hdr(0, hdr); ld_plane(0, 0, p0); ld_plane(0, 1, p1);
     x_load(0, xa_);
     x_store(0, xa_);
-    if (XDEEP && nchunk > 1) x_load(1, xa_);
     __syncthreads();
 
-    // LDS buffer of chunk kc = kc & 1.  In chunk kc: chunk kc+1 is in registers (requested during kc-1) and goes to the other
-    // buffer at the end of kc (that buffer was last read during kc-1); chunk kc+2 is requested in the middle of kc into the
-    // register set that was stored at the end of kc-1.
+    // LDS buffer of chunk kc = kc & 1.  In chunk kc: chunk kc+1 is requested at the top and goes to the other buffer at the end
+    // of kc (that buffer was last read during kc-1).
     for (int kb = 0; kb < nkb; ++kb) {
 #pragma unroll
       for (int c = 0; c < 4; ++c) {                                   // compile-time chunk index: every select below is static
         const int kc = 4 * kb + c;
-        // register set of chunk kc+1 (requested one chunk ago): xb_ in odd chunks, xa_ in even ones; the other set is free
-        // and takes chunk kc+2.  (Selected with `if` on the unrolled c, not through a reference: a selected reference keeps
-        // both arrays in scratch memory.)
         const int buf = c & 1, buf_next = buf ^ 1;
         const uint8_t* Ab = smem + (size_t)buf * BUFB;
         // (1) this chunk's first-half A fragments leave LDS first: nothing below may delay them
@@ -312,7 +295,7 @@ __global__ void __launch_bounds__(WM * WN * 64, 1) qpg_gemm_kernel(const QmmArgs
             }
         };
         a_read(0);
-        if (!XDEEP && kc + 1 < nchunk && !(QMM_DBG(a) & 4)) x_load(kc + 1, xa_);   // one chunk ahead: requested at the top, stored at the bottom (ablation bit 4: none)
+        if (kc + 1 < nchunk) x_load(kc + 1, xa_);                     // one chunk ahead: requested at the top, stored at the bottom
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
             const int j = 2 * c + h;                                  // sub-block of the k-block
@@ -324,17 +307,13 @@ __global__ void __launch_bounds__(WM * WN * 64, 1) qpg_gemm_kernel(const QmmArgs
                 const uint32_t w0 = (c & 1) ? pl.z : pl.x, w1 = (c & 1) ? pl.w : pl.y;
                 const uint32_t s0 = hdr[nt].y, s2 = hdr[nt].w;
                 const uint32_t scw = (j < 4) ? (s0 & 0x3F3F3F3Fu) : ((s2 & 0x0F0F0F0Fu) | ((s0 >> 2) & 0x30303030u));
-                if (!(QMM_DBG(a) & 2)) bf[nt] = qpg_frag_q4k(w0, w1, h, (scw >> (8 * (j & 3))) & 0xFFu, Mk, Ck);
-                else bf[nt] = __builtin_bit_cast(qpg_h8, make_uint4(w0, w1, scw, Mk));      // ablation: no unpack
+                bf[nt] = qpg_frag_q4k(w0, w1, h, (scw >> (8 * (j & 3))) & 0xFFu, Mk, Ck);
             }
             if (h == 1) {
                 // the plane's last sub-block is unpacked: its registers take the NEXT k-block's bytes (>= 2 chunks ahead of use)
-                if (!(QMM_DBG(a) & 8)) {                                   // ablation bit 8: no weight stream
-                    if (c == 1 && kb + 1 < nkb) ld_plane(kb + 1, 0, p0);
-                    if (c == 3 && kb + 1 < nkb) ld_plane(kb + 1, 1, p1);
-                    if (c == 2 && kb + 1 < nkb) ld_hdr(kb + 1, hdrn);
-                }
-                if (XDEEP) { if (kc + 2 < nchunk) { if (c & 1) x_load(kc + 2, xa_); else x_load(kc + 2, xb_); } }
+                if (c == 1 && kb + 1 < nkb) ld_plane(kb + 1, 0, p0);
+                if (c == 3 && kb + 1 < nkb) ld_plane(kb + 1, 1, p1);
+                if (c == 2 && kb + 1 < nkb) ld_hdr(kb + 1, hdrn);
             }
             // (3) MFMAs: the hi (and lo) part of the m-tiles against the four B fragments (independent accumulators per tile pair)
 #pragma unroll
@@ -342,10 +321,8 @@ __global__ void __launch_bounds__(WM * WN * 64, 1) qpg_gemm_kernel(const QmmArgs
 #pragma unroll
                 for (int mt = 0; mt < MTW; ++mt)
 #pragma unroll
-                    for (int nt = 0; nt < NTW; ++nt) {
-                        if (!(QMM_DBG(a) & 1)) acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[mt][p], bf[nt], acc[mt][nt], 0, 0, 0);
-                        else acc[mt][nt][0] += (float)af[mt][p][0] * (float)bf[nt][0];          // ablation: no matrix core
-                    }
+                    for (int nt = 0; nt < NTW; ++nt)
+                        acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[mt][p], bf[nt], acc[mt][nt], 0, 0, 0);
             if (h == 0) a_read(1);                                    // second half's A fragments: issued behind the first half's MFMAs
         }
         if (c == 3) {
@@ -378,43 +355,9 @@ __global__ void __launch_bounds__(WM * WN * 64, 1) qpg_gemm_kernel(const QmmArgs
 #pragma unroll
             for (int nt = 0; nt < NTW; ++nt) hdr[nt] = hdrn[nt];
         }
-        if (kc + 1 < nchunk && !(QMM_DBG(a) & 4)) { if (XDEEP && (c & 1)) x_store(buf_next, xb_); else x_store(buf_next, xa_); }
-        if (!(QMM_DBG(a) & 16)) __syncthreads();                           // buffer of kc+1 is complete, buffer of kc is free again (ablation bit 16: no barrier)
+        if (kc + 1 < nchunk) x_store(buf_next, xa_);
+        __syncthreads();                                              // buffer of kc+1 is complete, buffer of kc is free again
       }
-    }
-    if constexpr (FEPI) {
-        // ---- the epilogue of qmm_epilogue_apply on the registers: value = y * (the token's power-of-two image scale) + bias
-        float* const aout = a.out;
-#pragma unroll
-        for (int mt = 0; mt < MTW; ++mt)
-#pragma unroll
-            for (int v = 0; v < 4; ++v) {
-                const int t = t0 + wm * WMR + mt * 16 + 4 * kg + v;
-                if (t >= a.B) continue;
-                const float rs = im.row_scale[t];
-                if (fsilu) {
-#pragma unroll
-                    for (int nt = 0; nt < NTW / 2; ++nt) {
-                        const int lrow = e_tile[nt] * 16 + n16;
-                        if (!have[nt] || lrow >= a.seg[0].n_rows) continue;
-                        float g = y[mt][nt][v] * rs, u = y[mt][nt + NTW / 2][v] * rs;
-                        if (a.bias) { g += a.bias[a.seg[0].row0 + lrow]; u += a.bias[a.seg[1].row0 + lrow]; }
-                        aout[(size_t)t * a.ldo + lrow] = silu_f(g) * u;
-                    }
-                } else {
-#pragma unroll
-                    for (int nt = 0; nt < NTW; ++nt) {
-                        const int lrow = e_tile[nt] * 16 + n16;
-                        if (!have[nt] || lrow >= a.seg[e_sg[nt]].n_rows) continue;
-                        const int orow = a.seg[e_sg[nt]].row0 + lrow;
-                        float val = y[mt][nt][v] * rs;
-                        if (a.bias) val += a.bias[orow];
-                        if (a.epi == MI355_EPI_RESID) val += a.resid[(size_t)t * a.ldo + orow];
-                        aout[(size_t)t * a.ldo + orow] = val;
-                    }
-                }
-            }
-        return;
     }
     // ---- C[t][slot*16 + n]: lane holds column n16 of its row tiles, rows 4kg+v of its m-tiles
 #pragma unroll

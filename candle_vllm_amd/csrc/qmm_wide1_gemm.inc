@@ -1,138 +1,16 @@
-// Wide path (9..32 tokens), GEMM kernels of the single-plane generation + the split-K epilogue INSIDE the launch (round 4).
-// Included by qmatmul.hip after the epilogue helpers (QmgEpiRow, qmm_epilogue_apply, QmgChainOut) it reuses.
-//
-// EXPERIMENT of round 4, compiled into -DMI355_QMM_PROBES builds only (tuning key 49 = 1 there): the split-K epilogue INSIDE the GEMM
-// launch.  Rounds 2-3 ran `qmm_epilogue_kernel` as its own launch behind every wide GEMM: four launches of 5.7-8 us per layer at batch 32
-// (profiles/r03_b32_ragged_launch_groups.txt: 27 of the 166 us of a layer).  Here the partial sums go out write-through, every
-// workgroup drains them and takes one ticket per 256-column block of the output it contributed to, and the workgroup that arrives last
-// for a block runs that block's epilogue -- the same code on the same operands in the same order as the epilogue kernel (bit-identical
-// results: tests green).  Hand-off form: relaxed agent-scope (write-through) stores -> s_waitcnt vmcnt(0) -> barrier -> one relaxed
-// ticket per block -> ONE acquire fence in the last arriver -> plain loads (MI355X_MICROARCH.md "splitk-seam" / "publish-large").
-// A block = 256 output columns = one (token, k-block) row set of the NEXT mat-mul's activation image, so the chained staging keeps
-// its numerics and its code.
-// MEASURED (profiles/r04_b32_wide_fuse_ab.txt): the ragged batch-32 step 5947 -> 2987 tok/s.  These launches are ONE round of
-// workgroups that finish together, so nothing overlaps the tail, and the tail runs on as many workgroups as the output has 256-column
-// blocks (16 for wo / down, 112 for gate/up) where the epilogue kernel spreads 512-3584 workgroups over the chip: the GEMM launches took
-// 56-78 us instead of 10-29.  The tail's mere presence cost the unfused launches 4 % (128 VGPRs, scratch): hence probe builds only.
-// What a fused epilogue needs instead is per-TILE completion (the wave that finishes a row tile last applies the epilogue from its
-// registers), which the per-(token, k-block) block scale of the activation image does not allow (256 columns = 16 tiles of 3-4
-// workgroups): DESIGN.md section 7.
+// The GEMM kernels of the 9..32-token path (single-plane generation): split-K partial sums, finished by qmm_epilogue_kernel in its own launch.
+// (Running that epilogue inside the GEMM launch, per 256-column block or per row tile, was measured in round 4 and lost: DESIGN_HISTORY.md.)
+// Included by qmatmul.hip after QmgChainOut.
+
+// The kernels below read none of this: the argument keeps its place so that their kernel-argument layout stays as it was validated.
 struct QwFuse {
-    unsigned* ticket;            // [ceil(ldp / 256)] zero-initialised, reset by the last arriver; null = separate epilogue launch
-    const float* ssp;            // [nkb][BP] sum-of-squares partials of THIS launch's activations (fused RMSNorm)
-    QmgChainOut ch;              // image of the next wide mat-mul (img == null: no chain)
-    unsigned* tile_ticket;       // TEPI kernels: [slots] one arrival counter per row tile (zero-initialised, reset by the last arriver)
+    unsigned* ticket;
+    const float* ssp;
+    QmgChainOut ch;
+    unsigned* tile_ticket;
     int ks, n_runs;
-    int run_lo[3], run_hi[3];    // slot ranges of the launches (or launch halves) of this mat-mul: workgroup x of a run owns QMG_NC slots
+    int run_lo[3], run_hi[3];
 };
-
-__host__ __device__ __forceinline__ int qw1_wgs_touching(const QwFuse& fz, const int blk) {
-    int n = 0;
-    const int a0 = blk * 16, b0 = a0 + 16;
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-        if (r >= fz.n_runs) break;
-        const int lo = fz.run_lo[r], a = a0 > lo ? a0 : lo, b = b0 < fz.run_hi[r] ? b0 : fz.run_hi[r];
-        if (a < b) n += (b - 1 - lo) / QMG_NC - (a - lo) / QMG_NC + 1;
-    }
-    return n;
-}
-
-// host-side view for tests (tests/test_cpu_wide_fuse.py): how many workgroups (per k-split) contribute to block `blk`
-extern "C" int32_t mi355_internal_qw1_wgs_touching(int32_t n_runs, const int32_t* run_lo, const int32_t* run_hi, int32_t blk) {
-    QwFuse fz{};
-    fz.n_runs = n_runs < 3 ? n_runs : 3;
-    for (int r = 0; r < fz.n_runs; ++r) { fz.run_lo[r] = run_lo[r]; fz.run_hi[r] = run_hi[r]; }
-    return qw1_wgs_touching(fz, blk);
-}
-
-// the epilogue of output columns [256 blk, 256 blk + 256) for every token row, by one workgroup of 512 threads: what BP workgroups of
-// qmm_epilogue_kernel do (same per-element arithmetic, same order)
-// (forceinline: a call would take the kernel's descriptor by address, i.e. copy it to scratch, and every segment lookup of the main
-//  loop would become a scratch load -- measured: the whole launch 4 x slower)
-template <int MT>
-__device__ __forceinline__ void qw1_epilogue_block(const QmmArgs& a, const QwFuse& fz, const float* __restrict__ part, const int ldp,
-                                                   const int blk, uint8_t* __restrict__ smem) {
-    constexpr int BP = MT * 16, TB = 8;
-    float* sm_o = reinterpret_cast<float*>(smem);                       // [BP][256] outputs of the block (chain staging)
-    float* sm_inv = sm_o + BP * 256;                                    // [BP]
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int ks = fz.ks, nkb = a.K >> 8;
-    // ---- deferred RMSNorm factor of every token: the per-k-block partial sums by the lanes of one wave (as the epilogue kernel does)
-    for (int b = wave; b < BP; b += 8) {
-        float inv = 1.f;
-        if (a.norm_w && fz.ssp) {
-            float ss = 0.f;
-            if (b < a.B)
-                for (int kb = lane; kb < nkb; kb += 64) ss += fz.ssp[(size_t)kb * BP + b];
-            ss = wave_sum(ss);
-            inv = rsqrtf(ss / (float)a.K + a.eps);
-        }
-        if (lane == 0) sm_inv[b] = inv;
-    }
-    // ---- this thread's output column: segment, row, partner column (SiLU * up / RoPE), bias
-    const int col = tid & 255, half = tid >> 8;
-    const int prow = blk * 256 + col;
-    QmgEpiRow e0;
-    e0.sg = 0; e0.lrow = prow;
-    bool colok = prow < ldp;
-    if (colok) {
-        while (e0.sg + 1 < a.nseg && e0.lrow >= a.seg[e0.sg].n_tiles * 16) { e0.lrow -= a.seg[e0.sg].n_tiles * 16; ++e0.sg; }
-        colok = e0.lrow < a.seg[e0.sg].n_rows;
-    }
-    e0.orow = colok ? a.seg[e0.sg].row0 + e0.lrow : 0;
-    e0.has_aux = false; e0.s_main = e0.s_aux = e0.b_main = e0.b_aux = e0.resid = 0.f;
-    int aux = 0, aux_orow = 0;
-    if (colok) {
-        if (a.epi == MI355_EPI_SILU_MUL) {
-            if (e0.sg != 0) colok = false;
-            else { e0.has_aux = true; aux = a.seg[0].n_tiles * 16 + e0.lrow; aux_orow = a.seg[1].row0 + e0.lrow; }
-        } else if (a.epi == MI355_EPI_QKV_ROPE_CACHE) {
-            if (e0.sg < 2 && (e0.lrow % a.D) < a.rot) { e0.has_aux = true; aux = prow ^ 1; aux_orow = e0.orow ^ 1; }
-        }
-    }
-    if (colok && a.bias) { e0.b_main = a.bias[e0.orow]; if (e0.has_aux) e0.b_aux = a.bias[aux_orow]; }
-    e0.live = colok;
-    __syncthreads();                                                    // sm_inv
-    const bool chain = fz.ch.img != nullptr && blk * 256 < fz.ch.K;
-#pragma unroll 1
-    for (int t0 = 0; t0 < BP / 2; t0 += TB) {
-        float sm[TB], sa[TB], rs[TB];
-#pragma unroll
-        for (int i = 0; i < TB; ++i) {
-            const int b = half * (BP / 2) + t0 + i;
-            sm[i] = 0.f; sa[i] = 0.f; rs[i] = 0.f;
-            if (colok && b < a.B) {
-                for (int k = 0; k < ks; ++k) {
-                    sm[i] += part[((size_t)k * BP + b) * ldp + prow];
-                    if (e0.has_aux) sa[i] += part[((size_t)k * BP + b) * ldp + aux];
-                }
-                if (a.epi == MI355_EPI_RESID) rs[i] = a.resid[(size_t)b * a.ldo + e0.orow];
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < TB; ++i) {
-            const int b = half * (BP / 2) + t0 + i;
-            float o = 0.f;
-            if (colok && b < a.B) {
-                QmgEpiRow e = e0;
-                e.s_main = sm[i]; e.s_aux = sa[i]; e.resid = rs[i];
-                o = qmm_epilogue_apply(a, e, sm_inv[b], b);
-            }
-            if (chain) sm_o[b * 256 + col] = o;
-        }
-    }
-    if (!chain) return;
-    __syncthreads();
-    // ---- the next mat-mul's image row (token b, k-block blk): 32 threads build its 32 entries (qw1_prep_entry: block scale, sums)
-    const int El = tid & 31;
-    for (int b = tid >> 5; b < BP; b += 16) {
-        float v[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) v[i] = sm_o[b * 256 + El * 8 + i];
-        qw1_prep_entry(fz.ch.img, fz.ch.ssp, v, b < a.B, fz.ch.norm_w, fz.ch.MT, fz.ch.kbb, blk, b, El);
-    }
-}
 
 // QW1_LEAD: k-blocks of the activation image in flight ahead of the one the consumers work on (ring of QW1_LEAD + 1 LDS stages).
 // 2 since round 4: the skeleton of the gate/up launch (tools/probe_wide_stream.hip: weights + 18 KB image DMA + stores + LDS reads, no
@@ -147,20 +25,10 @@ __device__ __forceinline__ void qw1_epilogue_block(const QmmArgs& a, const QwFus
 #define QW1_LEAD 2
 #endif
 #define QW1_NB (QW1_LEAD + 1)
-#ifdef MI355_QMM_PROBES
-#define QW1_FUSE_BUILD 1
-#else
-#define QW1_FUSE_BUILD 0
-#endif
-// TEPI (round 4 EXPERIMENT, probe builds, key 49 = 2; lost its A/B -- see qw1_launch): the epilogue per ROW TILE inside the launch, for mat-muls whose epilogue stages no image (q|k|v: RoPE + cache write;
-// the lm_head; unchained stores).  A tile's k-splits leave their partial sums write-through and take a ticket on the tile; the WAVE that
-// arrives last sums the splits 0..ks-1 from memory (the epilogue kernel's order: bit-identical) and applies qmm_epilogue_apply to the
-// eight elements it holds -- the RoPE partner column is the neighbouring lane.  As parallel as the GEMM itself (one wave per tile), unlike
-// the per-256-column-block tail above; the deferred RMSNorm factors are summed by the loader wave while its first DMA is in flight.
-template <int MT, int WT, bool TEPI = false, int NC = QMG_NC, bool GRP = false>
+template <int MT, int WT, int NC = QMG_NC, bool GRP = false>
 __device__ __forceinline__ void qw1_gemm_body(const QmmArgs& a, const uint8_t* __restrict__ img, float* __restrict__ part, const int ldp,
                                               const int s0, const int s1, const int n_slots, const int slot_base, const int bx,
-                                              const QwFuse& fz, const int nb = MT * 16) {
+                                              const int nb = MT * 16) {
     // (nb, grouped launches: the group's live token rows -- the partial sums of the rows past them are never read)
     extern __shared__ __attribute__((aligned(1024))) uint8_t smem[];
     constexpr int BP = MT * 16;
@@ -169,7 +37,7 @@ __device__ __forceinline__ void qw1_gemm_body(const QmmArgs& a, const uint8_t* _
     const size_t kbb = (((size_t)MT * (16 * 32 * 16 + 512 + 64)) + 1023) / 1024 * 1024;
     const int kb_per = (nkb + gridDim.y - 1) / gridDim.y;
     const int kb_lo = blockIdx.y * kb_per, kb_hi = min(nkb, kb_lo + kb_per);         // never empty: the launcher normalises the split
-    const size_t stb = kbb, ring_bytes = QW1_NB * stb;                               // one stage = the image of one k-block
+    const size_t stb = kbb;                                                          // one stage = the image of one k-block
     if (wave == NC) {
         // loader wave: the images of the next QW1_LEAD k-blocks are in flight while the consumers work on kb
         constexpr int nchunk = (int)(((size_t)MT * (16 * 32 * 16 + 512 + 64) + 1023) / 1024);      // 1 KiB = one wave-wide 16-B DMA
@@ -184,8 +52,8 @@ __device__ __forceinline__ void qw1_gemm_body(const QmmArgs& a, const uint8_t* _
         // the loader's barrier: with QW1_LEAD == 2 the bare instruction -- the release fence of __syncthreads() makes the compiler drain
         // every DMA (`s_waitcnt vmcnt(0)`) in front of the s_barrier; what has to have landed is waited for by count just before
         auto loader_barrier = [&]() {
-            if constexpr (QW1_LEAD >= 2 && !TEPI) __builtin_amdgcn_s_barrier();
-            else __syncthreads();                                         // (TEPI: the loader also wrote sm_inv)
+            if constexpr (QW1_LEAD >= 2) __builtin_amdgcn_s_barrier();
+            else __syncthreads();
         };
         // "everything but the k-block requested last has landed": DMAs complete in order, one request = NI instructions
         // "everything but the `ahead` stages requested last has landed": DMAs complete in order, one stage = NI instructions
@@ -199,33 +67,7 @@ __device__ __forceinline__ void qw1_gemm_body(const QmmArgs& a, const uint8_t* _
 #pragma unroll
         for (int i = 0; i < QW1_LEAD; ++i)
             if (i < len) dma_kb(kb_lo + i, i);
-        if constexpr (TEPI) {
-            // deferred RMSNorm factor of every token row, as qmm_epilogue_kernel computes it (lane kb holds k-block kb's partial, then the
-            // same wave_sum): ALL rows' partials are requested before the first sum -- one memory round trip, not one per row (a loop of
-            // 32 dependent round trips in front of the first barrier cost the launch 24 us)
-            float* sm_inv = reinterpret_cast<float*>(smem + ring_bytes);
-            if (a.norm_w && fz.ssp) {
-                float ss[BP];
-#pragma unroll
-                for (int b = 0; b < BP; ++b) ss[b] = 0.f;
-                for (int kb = lane; kb < nkb; kb += 64) {             // (one pass for K <= 16384)
-                    const float4* row = reinterpret_cast<const float4*>(fz.ssp + (size_t)kb * BP);
-#pragma unroll
-                    for (int q = 0; q < BP / 4; ++q) {
-                        const float4 v4 = row[q];
-                        ss[4 * q] += v4.x; ss[4 * q + 1] += v4.y; ss[4 * q + 2] += v4.z; ss[4 * q + 3] += v4.w;
-                    }
-                }
-#pragma unroll
-                for (int b = 0; b < BP; ++b) {
-                    const float tot = wave_sum(b < a.B ? ss[b] : 0.f);
-                    if (lane == 0) sm_inv[b] = rsqrtf(tot / (float)a.K + a.eps);
-                }
-            } else if (lane < BP) {
-                sm_inv[lane] = 1.f;
-            }
-        }
-        wait_landed(TEPI ? 0 : min(QW1_LEAD, len) - 1);                  // the first stage (TEPI: its own loads above are counted too)
+        wait_landed(min(QW1_LEAD, len) - 1);                             // the first stage
         loader_barrier();
         int bufn = QW1_LEAD % QW1_NB;                                     // ring stage of k-block kb + QW1_LEAD
         for (int kb = kb_lo; kb < kb_hi; ++kb) {
@@ -271,93 +113,14 @@ __device__ __forceinline__ void qw1_gemm_body(const QmmArgs& a, const uint8_t* _
         }
         // the lane holds tokens 4kg + v of every m-tile for weight row rr: the partial sums of this k-split
         const int kg = lane >> 4, rr = lane & 15;
-        if constexpr (TEPI) {
-            if (have) {
-                const int ks = fz.ks;
-                float sum[MT][4];
-                if (ks > 1) {
-                    float* pp = part + (size_t)blockIdx.y * BP * ldp + (size_t)(slot_base + slot) * 16 + rr;
-#pragma unroll
-                    for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-                        for (int v = 0; v < 4; ++v)
-                            __hip_atomic_store(pp + (size_t)(16 * mt + 4 * kg + v) * ldp, y[mt][v], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                    unsigned tk = 0;
-                    if (lane == 0) tk = __hip_atomic_fetch_add(fz.tile_ticket + slot_base + slot, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    tk = __shfl(tk, 0, 64);
-                    if ((int)tk != ks - 1) return;                        // another k-split of this tile finishes it
-                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-                    if (lane == 0) __hip_atomic_store(fz.tile_ticket + slot_base + slot, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    const float* p0 = part + (size_t)(slot_base + slot) * 16 + rr;
-#pragma unroll
-                    for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-                        for (int v = 0; v < 4; ++v) {
-                            float acc = 0.f;
-                            for (int k = 0; k < ks; ++k) acc += p0[((size_t)k * BP + 16 * mt + 4 * kg + v) * ldp];
-                            sum[mt][v] = acc;
-                        }
-                } else {
-#pragma unroll
-                    for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-                        for (int v = 0; v < 4; ++v) sum[mt][v] = 0.f + y[mt][v];
-                }
-                const float* sm_inv = reinterpret_cast<const float*>(smem + ring_bytes);
-                QmgEpiRow e;
-                e.sg = sg; e.lrow = t * 16 + rr; e.orow = a.seg[sg].row0 + e.lrow;
-                e.live = e.lrow < a.seg[sg].n_rows;
-                e.has_aux = a.epi == MI355_EPI_QKV_ROPE_CACHE && sg < 2 && (e.lrow % a.D) < a.rot;
-                e.b_main = (e.live && a.bias) ? a.bias[e.orow] : 0.f;
-                e.b_aux = (e.live && a.bias && e.has_aux) ? a.bias[e.orow ^ 1] : 0.f;
-#pragma unroll
-                for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-                    for (int v = 0; v < 4; ++v) {
-                        const int b = 16 * mt + 4 * kg + v;
-                        const float partner = __shfl_xor(sum[mt][v], 1, 64);      // column ^ 1 of the same token: the RoPE pair
-                        e.s_main = sum[mt][v]; e.s_aux = partner;
-                        e.resid = (a.epi == MI355_EPI_RESID && e.live && b < a.B) ? a.resid[(size_t)b * a.ldo + e.orow] : 0.f;
-                        if (e.live && b < a.B) (void)qmm_epilogue_apply(a, e, sm_inv[b], b);
-                    }
-            }
-            return;
-        }
         if (have) {
             float* pp = part + (size_t)blockIdx.y * BP * ldp + (size_t)(slot_base + slot) * 16 + rr;
-            if (QW1_FUSE_BUILD && fz.ticket) {                            // write-through: the hand-off below needs no release fence
 #pragma unroll
-                for (int mt = 0; mt < MT; ++mt)
+            for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
-                    for (int v = 0; v < 4; ++v)
-                        __hip_atomic_store(pp + (size_t)(16 * mt + 4 * kg + v) * ldp, y[mt][v], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            } else {
-#pragma unroll
-                for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-                    for (int v = 0; v < 4; ++v)
-                        if (!GRP || 16 * mt + 4 * kg + v < nb) pp[(size_t)(16 * mt + 4 * kg + v) * ldp] = y[mt][v];
-            }
+                for (int v = 0; v < 4; ++v)
+                    if (!GRP || 16 * mt + 4 * kg + v < nb) pp[(size_t)(16 * mt + 4 * kg + v) * ldp] = y[mt][v];
         }
-    }
-    if (!QW1_FUSE_BUILD || !fz.ticket) return;
-    // ---- in-launch epilogue: drain, one ticket per 256-column block this workgroup contributed to, the last arriver finishes the block
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    const int tile_lo = slot_base + bx * NC, tile_hi = min(slot_base + n_slots, tile_lo + NC);
-    unsigned* sm_t = reinterpret_cast<unsigned*>(smem + ring_bytes - 16);    // past sm_o / sm_inv of qw1_epilogue_block
-    for (int blk = tile_lo >> 4; blk <= (tile_hi - 1) >> 4; ++blk) {
-        if (threadIdx.x == 0)
-            sm_t[0] = __hip_atomic_fetch_add(fz.ticket + blk, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __syncthreads();
-        const unsigned tk = sm_t[0];
-        __syncthreads();                                                  // sm_t is rewritten for the next block
-        if ((int)tk != fz.ks * qw1_wgs_touching(fz, blk) - 1) continue;  // uniform for the workgroup
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-        if (threadIdx.x == 0) __hip_atomic_store(fz.ticket + blk, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        qw1_epilogue_block<MT>(a, fz, part, ldp, blk, smem);
-        __syncthreads();                                                  // LDS is reused by the next block
     }
 }
 template <int MT, int WT>
@@ -368,37 +131,8 @@ __global__ void __launch_bounds__(512, 4) qw1_gemm_kernel(const QmmArgs a, const
     QMM_BURST_VALS(img, part, ldp, fz.ticket, fz.ssp, fz.ks);
     QMM_BURST_VALS(n_slots, slot_base);
     if (a.rows_dev && *a.rows_dev <= a.rows_min) return;
-    qw1_gemm_body<MT, WT>(a, img, part, ldp, 0, a.nseg, n_slots, slot_base, (int)blockIdx.x, fz);
+    qw1_gemm_body<MT, WT>(a, img, part, ldp, 0, a.nseg, n_slots, slot_base, (int)blockIdx.x);
 }
-#if QW1_FUSE_BUILD
-// the same with the per-tile epilogue (TEPI, probe builds): no epilogue launch follows
-template <int MT, int WT>
-__global__ void __launch_bounds__(512, 4) qw1_gemm_tepi_kernel(const QmmArgs a, const uint8_t* __restrict__ img, float* __restrict__ part,
-                                                               const int ldp, const int n_slots, const int slot_base, const int s0, const int s1,
-                                                               const QwFuse fz) {
-    if (a.rows_dev && *a.rows_dev <= a.rows_min) return;
-    qw1_gemm_body<MT, WT, true>(a, img, part, ldp, s0, s1, n_slots, slot_base, (int)blockIdx.x, fz);
-}
-template <int MT, int WTA, int WTB>
-__global__ void __launch_bounds__(512, 2) qw1_gemm2_tepi_kernel(const QmmArgs a, const uint8_t* __restrict__ img, float* __restrict__ part,
-                                                                const int ldp, const int s_split, const int slots0, const int slots1, const QwFuse fz) {
-    if (a.rows_dev && *a.rows_dev <= a.rows_min) return;
-    const int nwg0 = (slots0 + QMG_NC - 1) / QMG_NC;
-    if ((int)blockIdx.x < nwg0) qw1_gemm_body<MT, WTA, true>(a, img, part, ldp, 0, s_split, slots0, 0, (int)blockIdx.x, fz);
-    else qw1_gemm_body<MT, WTB, true>(a, img, part, ldp, s_split, a.nseg, slots1, slots0, (int)blockIdx.x - nwg0, fz);
-}
-#endif
-#if QW1_FUSE_BUILD
-// one run of same-type segments [s0, s1) of a mat-mul that takes several launches (the descriptor stays whole: the in-launch epilogue
-// of a block may finish columns of another run)
-template <int MT, int WT>
-__global__ void __launch_bounds__(512, 4) qw1_gemm_run_kernel(const QmmArgs a, const uint8_t* __restrict__ img, float* __restrict__ part,
-                                                              const int ldp, const int n_slots, const int slot_base, const int s0, const int s1,
-                                                              const QwFuse fz) {
-    if (a.rows_dev && *a.rows_dev <= a.rows_min) return;
-    qw1_gemm_body<MT, WT>(a, img, part, ldp, s0, s1, n_slots, slot_base, (int)blockIdx.x, fz);
-}
-#endif
 // q, k (Q4_K) + v (Q6_K) in one launch: a uniform branch between two specialised bodies (generation three's rule)
 template <int MT, int WTA, int WTB>
 __global__ void __launch_bounds__(512, 2) qw1_gemm2_kernel(const QmmArgs a, const uint8_t* __restrict__ img, float* __restrict__ part,
@@ -409,8 +143,8 @@ __global__ void __launch_bounds__(512, 2) qw1_gemm2_kernel(const QmmArgs a, cons
     QMM_BURST_VALS(s_split, slots0, slots1);
     if (a.rows_dev && *a.rows_dev <= a.rows_min) return;
     const int nwg0 = (slots0 + QMG_NC - 1) / QMG_NC;
-    if ((int)blockIdx.x < nwg0) qw1_gemm_body<MT, WTA>(a, img, part, ldp, 0, s_split, slots0, 0, (int)blockIdx.x, fz);
-    else qw1_gemm_body<MT, WTB>(a, img, part, ldp, s_split, a.nseg, slots1, slots0, (int)blockIdx.x - nwg0, fz);
+    if ((int)blockIdx.x < nwg0) qw1_gemm_body<MT, WTA>(a, img, part, ldp, 0, s_split, slots0, 0, (int)blockIdx.x);
+    else qw1_gemm_body<MT, WTB>(a, img, part, ldp, s_split, a.nseg, slots1, slots0, (int)blockIdx.x - nwg0);
 }
 // grouped launches (QwGroup, qmm_wide1.inc): blockIdx.z = the group; image and partial sums of the group, its own row gate
 template <int MT, int WT>
@@ -424,8 +158,8 @@ __global__ void __launch_bounds__(512, 4) qw1_gemm_grp_kernel(const QmmArgs a, c
     const int e = blockIdx.z;
     const int nb = a.rows_dev ? min(a.B, a.rows_dev[e] - a.rows_min) : a.B;
     if (nb <= 0) return;
-    qw1_gemm_body<MT, WT, false, QMG_NC, true>(a, img + (size_t)e * g.img, part + (size_t)e * g.part, ldp, 0, a.nseg, n_slots, slot_base,
-                                               (int)blockIdx.x, fz, nb);
+    qw1_gemm_body<MT, WT, QMG_NC, true>(a, img + (size_t)e * g.img, part + (size_t)e * g.part, ldp, 0, a.nseg, n_slots, slot_base,
+                                               (int)blockIdx.x, nb);
 }
 template <int MT, int WTA, int WTB>
 __global__ void __launch_bounds__(512, 2) qw1_gemm2_grp_kernel(const QmmArgs a, const uint8_t* __restrict__ img, float* __restrict__ part,
@@ -440,6 +174,6 @@ __global__ void __launch_bounds__(512, 2) qw1_gemm2_grp_kernel(const QmmArgs a, 
     if (nb <= 0) return;
     const int nwg0 = (slots0 + QMG_NC - 1) / QMG_NC;
     img += (size_t)e * g.img; part += (size_t)e * g.part;
-    if ((int)blockIdx.x < nwg0) qw1_gemm_body<MT, WTA, false, QMG_NC, true>(a, img, part, ldp, 0, s_split, slots0, 0, (int)blockIdx.x, fz, nb);
-    else qw1_gemm_body<MT, WTB, false, QMG_NC, true>(a, img, part, ldp, s_split, a.nseg, slots1, slots0, (int)blockIdx.x - nwg0, fz, nb);
+    if ((int)blockIdx.x < nwg0) qw1_gemm_body<MT, WTA, QMG_NC, true>(a, img, part, ldp, 0, s_split, slots0, 0, (int)blockIdx.x, nb);
+    else qw1_gemm_body<MT, WTB, QMG_NC, true>(a, img, part, ldp, s_split, a.nseg, slots1, slots0, (int)blockIdx.x - nwg0, nb);
 }

@@ -9,7 +9,6 @@ enum {
     MI355_SCR_QMM_IMG0 = 3,      // wide mat-mul path: activation image, buffer 0 / 1
     MI355_SCR_QMM_IMG1 = 4,
     MI355_SCR_QMM_PART = 5,      // wide mat-mul path: split-K partial sums
-    MI355_SCR_QMM_TICKET = 6,    // wide mat-mul path: split-K arrival tickets (zero-initialised, self-cleaning)
     MI355_SCR_QMP_WS = 7,        // prompt-step GEMM: quantised activation image
     MI355_SCR_DENSE_WS = 8,      // dense / GPTQ path staging
     MI355_SCR_COMM = 9,          // one-shot all-reduce staging

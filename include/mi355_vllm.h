@@ -304,7 +304,7 @@ int mi355_moe_gather(float* dst, const float* src, const int32_t* perm, int32_t 
 int mi355_moe_scatter_combine(float* ys, const float* y_sorted, const float* weights, const int32_t* inv, int32_t num_tokens,
                               int32_t hidden, int32_t top_k, int64_t stream);
 /* A/B switches (process-global; for measurements and for tests that drive an alternative kernel through the same entry point).
- * No product path depends on a non-default value.  The PRODUCT library honours exactly these ten keys:
+ * No product path depends on a non-default value.  The library honours exactly these ten keys:
  *    3  decode-attention partition merge: low 4 bits 0 = separate reduce launch, 1 = in the last arriver where it pays (default),
  *       2 = always; bits 4.. = partitions per workgroup (0 = chosen per launch, else 1 | 4 | 8 | 16)
  *    5  decode-attention partition size of the step drivers (0 = their own choice: 32, or 64 for the balanced stream)
@@ -322,33 +322,15 @@ int mi355_moe_scatter_combine(float* ys, const float* y_sorted, const float* wei
  *       with partition size 64; 2 = additionally 1024 / 2048 / 4096 through the chunked LDS-DMA kernel
  *   47  prompt attention: bit 0 = K / V through the LDS ring (bf16 cache, head_dim 128; default 1), bit 1 = fp8 caches on the generic kernel
  *   48  Q4_K prompt-step launches apply store / residual / SiLU * up in the GEMM's store loop (1, default)
- * mi355_tuning_supported(key) = 1 for these; mi355_get_tuning returns their live value.  Every other key (0-2, 8, 10-23, 33-38, 42, 49:
- * wave / tile / split geometry, ablation modes, the experiments that lost their A/B) exists in probe builds only
- * (-DMI355_QMM_PROBES, tools/build_probe_lib.sh, listed next to their variables in csrc/); the product library ignores them
- * (mi355_get_tuning: INT32_MIN). */
+ * mi355_tuning_supported(key) = 1 for these; mi355_get_tuning returns their live value.  Other keys are ignored and
+ * mi355_get_tuning returns INT32_MIN for them. */
 void mi355_set_tuning(int32_t key, int32_t value);
 int32_t mi355_get_tuning(int32_t key);
 int32_t mi355_tuning_supported(int32_t key);
-/* experiments only: device buffer of uint64 [workgroup][16 waves][4] that the 1..8-token mat-vec fills with wall-clock
- * stamps (entry, main loop done, past the barrier, exit) while probe mode 7 is set (probe builds only); NULL switches it off */
+/* experiments only: device buffer of uint64 [workgroup][16 waves][8] that the 1..8-token mat-vec of a timeline build
+ * (-DMI355_QMM_TIMELINE, tools/build_variant_lib.sh) fills with eight wall-clock stamps per wave; NULL switches it off.  The
+ * product library stores the pointer and never writes through it. */
 int mi355_debug_set_timestamps(void* dev_ptr);
-/* EXPERIMENTS, compiled into probe builds only (-DMI355_QMM_PROBES, tools/build_probe_lib.sh); in the product library the
- * three entry points below exist and refuse (hipErrorNotSupported / error word 0).
- * Single-token launches on an LDS-DMA loader / consumer engine (csrc/qmv_engine.inc; tuning keys 20 on / off, 21 consumer
- * waves, 22 ring KiB cap).  Its in-workgroup waits are bounded: a wait that gave up leaves a sticky device word (1 consumer
- * waited for data, 2 loader for ring space, 3 / 4 consumer rendezvous, 5 a chain edge) and the launch's outputs are garbage.
- * Reads the word into *out_host (synchronising copy) and clears it when reset != 0. */
-int mi355_qmv_error(int32_t* out_host, int32_t reset);
-/* A chain of n (<= 4) single-token launches in ONE persistent launch (csrc/qmv_chain.inc): descs[p + 1].x must be
- * descs[p].out (f32, one token); only the last may carry MI355_EPI_QKV_ROPE_CACHE.  This is the decode step's
- * wo + residual -> ffn_norm + gate/up + silu*mul -> down + residual -> next layer's attn_norm + q|k|v + RoPE + cache write
- * (quantized_llama.rs:424-506), bit-identical to the four mi355_qmatmul_fused calls.  `sync` = mi355_qmv_chain_sync_bytes()
- * bytes of device memory zeroed once (arrival counters, monotonic across launches and hipGraph replays).  The launch needs
- * every CU of the device to itself (one resident workgroup per CU; the phase boundaries are grid-wide dependencies with
- * bounded waits, mi355_qmv_error).  Returns hipErrorNotSupported (801) when the chain does not fit -- issue the calls one by
- * one then.  Tuning key 23 = 1 switches chaining on (probe builds; measured slower than launch by launch). */
-int mi355_qmv_chain_sync_bytes(void);
-int mi355_qmatmul_chain(const mi355_qmm_desc* descs, int32_t n, void* sync, int64_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * 3b. Safetensors path: dense 16-bit and GPTQ/AWQ/Marlin 4-bit linears (decode-shaped, any num_tokens).

@@ -62,16 +62,9 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=1)
     ap.add_argument("--ctx", type=int, default=4608)
-    ap.add_argument("--nw", type=int, default=0)
-    ap.add_argument("--r", type=int, default=0)
-    ap.add_argument("--dbg", type=int, default=0)
     ap.add_argument("--only-qmm", action="store_true")
     args = ap.parse_args()
     dev = "cuda"
-    cv.lib.mi355_set_tuning(0, args.nw)
-    cv.lib.mi355_set_tuning(1, args.r)
-    cv.lib.mi355_set_tuning(2, args.dbg)
-    print(f"tuning nw={args.nw} r={args.r} dbg={args.dbg}", flush=True)
     B = args.batch
     hid, I, H, Hkv, D, V = 4096, 14336, 32, 8, 128, 128256
     flush = torch.zeros(128 * 1024 * 1024, dtype=torch.float32, device=dev)

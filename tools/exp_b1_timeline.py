@@ -3,7 +3,7 @@ single-token mat-vec kernel (qmm_kernel<1, R, ...>; -DMI355_QMM_TIMELINE build: 
 launch groups q|k|v (+ RoPE + cache write), wo, gate/up, down of one Llama-3-8B layer at ctx 4096:
    0 wave entry  1 kernarg fields in SGPRs  2 prologue loads issued  3 first k-block staged (x, norm weight arrived)
    4 first (k-block, tile) unit computed (first weights arrived)  5 main loop done  6 past the workgroup barrier  7 epilogue done
-Run:  MI355_LIB_PATH=$PWD/build_probe/libmi355vllm_tl.so python tools/exp_b1_timeline.py"""
+Run:  MI355_LIB_PATH=$PWD/build_variant/libmi355vllm_tl.so python tools/exp_b1_timeline.py"""
 import os, sys
 import numpy as np
 import torch

@@ -1,5 +1,5 @@
 """Which launch group of the batch-1 step produces non-finite values (and how often)?  Full-size Llama-3-8B Q4_K_M shapes, ctx 4096, eager
-launch groups through mi355_llama_run_part, every activation buffer checked after every group.  NW = 0 (heuristic) and forced 2 / 4 / 8."""
+launch groups through mi355_llama_run_part, every activation buffer checked after every group."""
 import ctypes, os, sys
 import numpy as np
 import torch
@@ -37,23 +37,20 @@ def bad(name):
 
 reads = {0: ["q"], 1: ["attn"], 2: ["xs"], 3: ["h"], 4: ["xs"]}
 names = {0: "qkv", 1: "attention", 2: "wo", 3: "gateup", 4: "down"}
-for nw in (0, 8, 4, 2):
-    lib.mi355_set_tuning(0, nw)
-    fails = {}
-    for rep in range(int(os.environ.get("REPS", "6"))):
-        gm.decode_begin(np.array([5 + rep], np.uint32), np.full(1, CTX + 1, np.uint32), bt, ctx_cap=CTX + 16, stream=st)
-        _check(lib.mi355_llama_run_part(gm.h, 0, 6, st), "embed")
-        for l in range(cfg.n_layers):
-            for part in range(5):
-                _check(lib.mi355_llama_run_part(gm.h, l, part, st), "run_part")
-                torch.cuda.synchronize()
-                for b in reads[part]:
-                    n, idx, mx = bad(b)
-                    if n:
-                        fails.setdefault((names[part], b), []).append((rep, l, n, idx, mx))
-            if fails:
-                break
+fails = {}
+for rep in range(int(os.environ.get("REPS", "6"))):
+    gm.decode_begin(np.array([5 + rep], np.uint32), np.full(1, CTX + 1, np.uint32), bt, ctx_cap=CTX + 16, stream=st)
+    _check(lib.mi355_llama_run_part(gm.h, 0, 6, st), "embed")
+    for l in range(cfg.n_layers):
+        for part in range(5):
+            _check(lib.mi355_llama_run_part(gm.h, l, part, st), "run_part")
+            torch.cuda.synchronize()
+            for b in reads[part]:
+                n, idx, mx = bad(b)
+                if n:
+                    fails.setdefault((names[part], b), []).append((rep, l, n, idx, mx))
         if fails:
             break
-    print(f"NW={nw}: ", "clean" if not fails else {k: v[:3] for k, v in fails.items()}, flush=True)
-lib.mi355_set_tuning(0, 0)
+    if fails:
+        break
+print("clean" if not fails else {k: v[:3] for k, v in fails.items()}, flush=True)

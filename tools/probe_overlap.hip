@@ -1,8 +1,8 @@
 // Scratch micro-benchmark (not part of the product): can CONSECUTIVE launches of the single-token step overlap --
 // launch N+1 dispatched without waiting for N, streaming its first weights while N drains, the dependency carried through device
 // memory -- and what does that buy on a skeleton of the batch-1 step (same grids, same bytes, a dependent-FMA stand-in for the arithmetic)?
-//   hipcc --offload-arch=gfx950 -O3 -std=c++17 tools/probe_overlap.hip -o build_probe/probe_overlap
-//   build_probe/probe_overlap [fma_iters_per_load ...]          (AMD_LOG_LEVEL=4 build_probe/probe_overlap mini : the AQL headers)
+//   hipcc --offload-arch=gfx950 -O3 -std=c++17 tools/probe_overlap.hip -o build_variant/probe_overlap
+//   build_variant/probe_overlap [fma_iters_per_load ...]          (AMD_LOG_LEVEL=4 build_variant/probe_overlap mini : the AQL headers)
 // Hand-off forms:
 //   CTR : the producer stores its outputs write-through (sc1), drains, adds 1 to an arrival counter (8 shards); one wave per consumer
 //         workgroup polls the counters, then the workgroup loads the activations (sc1)

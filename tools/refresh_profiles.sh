@@ -62,8 +62,7 @@ for leg in bf16_b32 gptq_qwen2 gptq_qwen2_b32 mixtral_fp8 mixtral_fp8_b32; do
   [ -n "$f" ] && (echo "# commit $SHA : rocprofv3 --kernel-trace --stats -- python bench_legs.py $leg --no-parity ; $(grep '^{' $OUT/leg_$leg.log | tail -1 | grep -o '"value": [0-9.]*' | head -1) under rocprofv3"; head -16 "$f") > $OUT/${RN}_leg_${leg}_kernel_stats.csv
 done
 [ -n "$SKIP_MICRO" ] && { head -12 $OUT/${RN}_b32_ragged_launch_groups.txt | cut -c1-170; exit 0; }
-# 9. micro-benchmarks: bare weight stream of the wide GEMM; per-wave timelines of the single-token launches
+# 9. micro-benchmark: bare weight stream of the wide GEMM
 [ -x tools/probe_wide_stream.bin ] || hipcc --offload-arch=gfx950 -O3 tools/probe_wide_stream.hip -o tools/probe_wide_stream.bin
 (echo "# commit $SHA : tools/probe_wide_stream.bin"; timeout 120 tools/probe_wide_stream.bin) > $OUT/${RN}_probe_wide_stream.txt 2>&1
-(echo "# commit $SHA : MI355_LIB_PATH=build_probe/libmi355vllm_probes.so python tools/exp_wave_times.py (probe build: tools/build_probe_lib.sh; us since the first wave's entry; 100 MHz clock)"; MI355_LIB_PATH=$R/build_probe/libmi355vllm_probes.so timeout 300 python tools/exp_wave_times.py 2>&1 | grep -v amdgpu.ids) > $OUT/${RN}_b1_wave_times.txt
 head -12 $OUT/${RN}_b32_ragged_launch_groups.txt | cut -c1-170
