@@ -786,6 +786,7 @@ extern "C" int mi355_llama_set_moe_expert(void* mp, int32_t layer, int32_t which
     const int slot = which == MI355_W_W1 ? 0 : (which == MI355_W_W2 ? 1 : (which == MI355_W_W3 ? 2 : -1));
     if (slot < 0) return (int)hipErrorInvalidValue;
     Layer& L = m->layers[layer];
+    if (ggml_type == MI355_GGML_Q5_K) return (int)hipErrorNotSupported;   // the expert kernels (single-token and grouped) decode Q4_K / Q6_K only
     const int64_t n = mi355_qweight_repacked_size(ggml_type, n_rows, k);
     if (n < 0) return (int)hipErrorInvalidValue;
     if (!L.eslab[slot]) {
@@ -1159,7 +1160,7 @@ int load_gguf_impl(const char* path, int32_t max_batch, int32_t max_blocks_per_s
     if (info(n_expert > 1 ? "blk.0.ffn_gate.0.weight" : "blk.0.ffn_gate.weight", dff, &tff, &nbff) < 0) return (int)hipErrorInvalidValue;
 
     if (vocab <= 0 || vocab > (int64_t)lim || dff[0] <= 0 || dff[0] > (int64_t)lim) return (int)hipErrorInvalidValue;
-    if (ty != 0 && ty != MI355_GGML_Q4_K && ty != MI355_GGML_Q6_K) return (int)hipErrorNotSupported;   // token_embd: F32 or a k-quant we dequantise
+    if (ty != 0 && ty != MI355_GGML_Q4_K && ty != MI355_GGML_Q5_K && ty != MI355_GGML_Q6_K) return (int)hipErrorNotSupported;   // token_embd: F32 or a k-quant we dequantise
     mi355_llama_config cfg;
     memset(&cfg, 0, sizeof(cfg));
     cfg.hidden = (int32_t)embd; cfg.n_layers = (int32_t)block_count; cfg.n_heads = (int32_t)head_count;
@@ -1195,13 +1196,15 @@ int load_gguf_impl(const char* path, int32_t max_batch, int32_t max_blocks_per_s
         auto expect_q = [&](const std::string& name, int64_t rows, int64_t cols, int dim, int world) -> int {
             int64_t dd[4]; int32_t t; uint64_t n;
             if (info(name, dd, &t, &n) < 0) return (int)hipErrorInvalidValue;
-            if (t != MI355_GGML_Q4_K && t != MI355_GGML_Q6_K) return (int)hipErrorNotSupported;
+            if (t != MI355_GGML_Q4_K && t != MI355_GGML_Q5_K && t != MI355_GGML_Q6_K) return (int)hipErrorNotSupported;
+            if (t == MI355_GGML_Q5_K && dim < 0 && name.find("ffn_") != std::string::npos) return (int)hipErrorNotSupported;   // Mixtral expert tensors: the expert kernels decode Q4_K / Q6_K only
             if (dd[0] != rows || dd[1] != cols || dd[2] != 1 || dd[3] != 1) return (int)hipErrorInvalidValue;
             if (dim == 0 && world > 1) { if (rows % world) return (int)hipErrorInvalidValue; rows /= world; }
             if (dim == 1 && world > 1) { if (cols % world) return (int)hipErrorInvalidValue; cols /= world; }
             if (cols % 256) {
                 // a dim-1 shard that cuts a k-quant block is re-quantised to Q8_0 (quantized_var_builder.rs:234-269): 32-wide blocks
-                if (dim == 1 && world > 1) return (cols % 32) ? (int)hipErrorNotSupported : 0;
+                // (mi355_gguf_tensor_shard_q8_0 restates Q4_K / Q6_K only: a shard that cuts a Q5_K block is refused)
+                if (dim == 1 && world > 1) return ((cols % 32) || t == MI355_GGML_Q5_K) ? (int)hipErrorNotSupported : 0;
                 return (int)hipErrorInvalidValue;
             }
             // whole 16-row tiles are required only where the fused QKV epilogue needs them (mi355_qmatmul_fused checks the
@@ -1259,7 +1262,7 @@ int load_gguf_impl(const char* path, int32_t max_batch, int32_t max_blocks_per_s
         int64_t dd[4]; int32_t t; uint64_t n;
         const int i = info(name, dd, &t, &n);
         if (i < 0) return (int)hipErrorInvalidValue;
-        if (t != MI355_GGML_Q4_K && t != MI355_GGML_Q6_K) return (int)hipErrorNotSupported;   // other ggml types: out of scope
+        if (t != MI355_GGML_Q4_K && t != MI355_GGML_Q5_K && t != MI355_GGML_Q6_K) return (int)hipErrorNotSupported;   // other ggml types: out of scope
         if (dim < 0 || world <= 1)
             return mi355_llama_set_qweight(m, layer, which, t, mi355_gguf_tensor_data(g, i), (int32_t)dd[0], (int32_t)dd[1]);
         const int64_t bytes = mi355_gguf_tensor_shard(g, i, dim, rank, world, nullptr, 0);
@@ -1287,7 +1290,7 @@ int load_gguf_impl(const char* path, int32_t max_batch, int32_t max_blocks_per_s
     // token_embd: dequantised once (quantized_llama.rs:262-264)
     if (ty == 0) {
         RCHECK(mi355_llama_set_f32(m, -1, MI355_W_TOK_EMBD, static_cast<const float*>(mi355_gguf_tensor_data(g, i_embd)), vocab * (int64_t)embd));
-    } else if (ty == MI355_GGML_Q4_K || ty == MI355_GGML_Q6_K) {
+    } else if (ty == MI355_GGML_Q4_K || ty == MI355_GGML_Q5_K || ty == MI355_GGML_Q6_K) {
         void* native = nullptr;
         HCHECK(hipMalloc(&native, nb));
         HCHECK(hipMemcpy(native, mi355_gguf_tensor_data(g, i_embd), nb, hipMemcpyHostToDevice));
@@ -1310,7 +1313,7 @@ int load_gguf_impl(const char* path, int32_t max_batch, int32_t max_blocks_per_s
             int64_t dd[4]; int32_t t; uint64_t n;
             const int i = info(name, dd, &t, &n);
             if (i < 0) return (int)hipErrorInvalidValue;
-            if (t != MI355_GGML_Q4_K && t != MI355_GGML_Q6_K) return (int)hipErrorNotSupported;
+            if (t != MI355_GGML_Q4_K && t != MI355_GGML_Q5_K && t != MI355_GGML_Q6_K) return (int)hipErrorNotSupported;
             if (pad_vocab(vocab, tp_world) % tp_world != 0) return (int)hipErrorInvalidValue;   // (also refused by mi355_llama_create)
             const int64_t local = pad_vocab(vocab, tp_world) / tp_world;
             const int64_t bytes = mi355_gguf_tensor_rows_padded(g, i, (int64_t)tp_rank * local, local, nullptr, 0);

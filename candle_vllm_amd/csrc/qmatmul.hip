@@ -32,10 +32,13 @@
 #define Q6K_BLOCK 210
 #define Q4K_TILE (16 * Q4K_BLOCK)   // 2304
 #define Q6K_TILE (16 * Q6K_BLOCK)   // 3360
+#define Q5K_BLOCK 176
+#define Q5K_TILE (16 * Q5K_BLOCK)   // 2816
 #define BF16_128 0x43004300u        // two bf16 128.0 ; OR-ing a code q < 128 into the mantissa gives 128+q
 
-static inline int tile_bytes_of(int type) { return type == MI355_GGML_Q4_K ? Q4K_TILE : Q6K_TILE; }
-static inline int block_bytes_of(int type) { return type == MI355_GGML_Q4_K ? Q4K_BLOCK : Q6K_BLOCK; }
+static inline int tile_bytes_of(int type) { return type == MI355_GGML_Q4_K ? Q4K_TILE : (type == MI355_GGML_Q5_K ? Q5K_TILE : Q6K_TILE); }
+static inline int block_bytes_of(int type) { return type == MI355_GGML_Q4_K ? Q4K_BLOCK : (type == MI355_GGML_Q5_K ? Q5K_BLOCK : Q6K_BLOCK); }
+static inline bool is_kquant(int type) { return type == MI355_GGML_Q4_K || type == MI355_GGML_Q5_K || type == MI355_GGML_Q6_K; }
 
 // ================================================================================================
 // Host-side repack: native GGUF rows [N][K/256][block] -> tiles [ceil(N/16)][K/256][tile].
@@ -44,8 +47,13 @@ static inline int block_bytes_of(int type) { return type == MI355_GGML_Q4_K ? Q4
 //   Q6_K tile (3360 B): sc[16 rows][16 x i8] | ql_n0[64][16 B] | ql_n1[64][16 B] | qh[64][16 B] | d[16 x f16]
 //       ql_n lane = { ql[64n+4kg..+4], ql[64n+32+4kg..+4], ql[64n+16+4kg..+4], ql[64n+48+4kg..+4] }
 //       qh   lane = { qh[4kg..+4], qh[16+4kg..+4], qh[32+4kg..+4], qh[48+4kg..+4] }
+//   Q5_K tile (2816 B): hdr[16 rows][16 B] | qs_p0[64][16 B] | qs_p1[64][16 B] (as Q4_K) | qh[64 lanes][2 x u32]
+//       the lane's 64 fifth bits (elements l = 8kg + i, i = 0..7, of the eight sub-blocks j) are TRANSPOSED into the order
+//       the unpack consumes them: word h = i >> 2 ; bit 2j + (i & 1) + 16 ((i >> 1) & 1) = bit j of qh[8kg + i].  One
+//       shift by (2j + c - 4) and one AND with 0x00100010 then leave the fifth bits of the element pair (c, c + 2) of
+//       sub-block j at bit 4 of the two 16-bit halves: mantissa bit 4 of the bf16 code 128 + q and of the f16 code 1024 + q.
 extern "C" int64_t mi355_qweight_repacked_size(int32_t ggml_type, int64_t n_rows, int64_t k) {
-    if ((ggml_type != MI355_GGML_Q4_K && ggml_type != MI355_GGML_Q6_K) || k <= 0 || (k % 256) || n_rows <= 0) return -1;
+    if (!is_kquant(ggml_type) || k <= 0 || (k % 256) || n_rows <= 0) return -1;
     return ((n_rows + 15) / 16) * (k / 256) * (int64_t)tile_bytes_of(ggml_type);
 }
 
@@ -73,6 +81,22 @@ extern "C" int mi355_qweight_repack(void* dst_v, const void* src_v, int32_t ggml
                             memcpy(o, qs + 32 * (2 * p) + 8 * kg, 8);
                             memcpy(o + 8, qs + 32 * (2 * p + 1) + 8 * kg, 8);
                         }
+                } else if (ggml_type == MI355_GGML_Q5_K) {
+                    memcpy(t + r * 16, b, 16);
+                    const uint8_t *qh = b + 16, *qs = b + 48;
+                    for (int p = 0; p < 2; ++p)
+                        for (int kg = 0; kg < 4; ++kg) {
+                            uint8_t* o = t + 256 + p * 1024 + (kg * 16 + r) * 16;
+                            memcpy(o, qs + 32 * (2 * p) + 8 * kg, 8);
+                            memcpy(o + 8, qs + 32 * (2 * p + 1) + 8 * kg, 8);
+                        }
+                    for (int kg = 0; kg < 4; ++kg) {
+                        uint32_t hw[2] = {0, 0};
+                        for (int i = 0; i < 8; ++i)
+                            for (int j = 0; j < 8; ++j)
+                                hw[i >> 2] |= (uint32_t)((qh[8 * kg + i] >> j) & 1) << (2 * j + (i & 1) + 16 * ((i >> 1) & 1));
+                        memcpy(t + 2304 + (kg * 16 + r) * 8, hw, 8);
+                    }
                 } else {
                     const uint8_t *ql = b, *qh = b + 128, *sc = b + 192, *d = b + 208;
                     memcpy(t + r * 16, sc, 16);
@@ -114,6 +138,17 @@ __device__ __forceinline__ float dequant_native(int type, const uint8_t* __restr
         const uint8_t qb = blk[16 + 32 * g + l];
         const int q = (j & 1) ? (qb >> 4) : (qb & 0xF);
         return d * (float)sc * (float)q - dmin * (float)m;
+    } else if (type == MI355_GGML_Q5_K) {                    // f16 d, dmin | scales[12] as Q4_K | qh[32] | qs[128]
+        const float d = f16_bits_to_f32(*reinterpret_cast<const uint16_t*>(blk));
+        const float dmin = f16_bits_to_f32(*reinterpret_cast<const uint16_t*>(blk + 2));
+        const uint8_t* s = blk + 4;
+        const int j = i >> 5, l = i & 31;
+        int sc, m;
+        if (j < 4) { sc = s[j] & 63; m = s[j + 4] & 63; }
+        else { sc = (s[j + 4] & 0xF) | ((s[j - 4] >> 6) << 4); m = (s[j + 4] >> 4) | ((s[j] >> 6) << 4); }
+        const uint8_t qb = blk[48 + 32 * (j >> 1) + l];
+        const int q = ((j & 1) ? (qb >> 4) : (qb & 0xF)) | (((blk[16 + l] >> j) & 1) << 4);
+        return d * (float)sc * (float)q - dmin * (float)m;
     } else {
         const uint8_t *ql = blk, *qh = blk + 128;
         const int8_t* sc = reinterpret_cast<const int8_t*>(blk + 192);
@@ -129,12 +164,12 @@ __device__ __forceinline__ float dequant_native(int type, const uint8_t* __restr
 
 __global__ void __launch_bounds__(256) dequantize_native_kernel(float* __restrict__ out, const uint8_t* __restrict__ w,
                                                                 int type, int64_t n_blocks) {
-    const int bb = (type == MI355_GGML_Q4_K) ? Q4K_BLOCK : Q6K_BLOCK;
+    const int bb = (type == MI355_GGML_Q4_K) ? Q4K_BLOCK : (type == MI355_GGML_Q5_K ? Q5K_BLOCK : Q6K_BLOCK);
     for (int64_t b = blockIdx.x; b < n_blocks; b += gridDim.x)
         out[b * 256 + threadIdx.x] = dequant_native(type, w + b * bb, threadIdx.x);
 }
 extern "C" int mi355_dequantize(float* out, const void* w_native, int32_t ggml_type, int64_t n_elems, int64_t stream) {
-    if ((ggml_type != MI355_GGML_Q4_K && ggml_type != MI355_GGML_Q6_K) || (n_elems % 256)) return (int)hipErrorInvalidValue;
+    if (!is_kquant(ggml_type) || (n_elems % 256)) return (int)hipErrorInvalidValue;
     if (n_elems == 0) return 0;
     const int64_t nb = n_elems / 256;
     hipLaunchKernelGGL(dequantize_native_kernel, dim3((unsigned)(nb < 65535 ? nb : 65535)), dim3(256), 0,
@@ -145,7 +180,7 @@ extern "C" int mi355_dequantize(float* out, const void* w_native, int32_t ggml_t
 // one wave per (row, token): y[t][row] = sum_k x[t][k] * dequant(W[row][k])
 __global__ void __launch_bounds__(256) qmatmul_ref_kernel(float* __restrict__ out, const float* __restrict__ x,
                                                           const uint8_t* __restrict__ w, int type, int T, int N, int K) {
-    const int bb = (type == MI355_GGML_Q4_K) ? Q4K_BLOCK : Q6K_BLOCK;
+    const int bb = (type == MI355_GGML_Q4_K) ? Q4K_BLOCK : (type == MI355_GGML_Q5_K ? Q5K_BLOCK : Q6K_BLOCK);
     const int lane = threadIdx.x & 63;
     const int64_t wid = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (wid >= (int64_t)T * N) return;
@@ -159,7 +194,7 @@ __global__ void __launch_bounds__(256) qmatmul_ref_kernel(float* __restrict__ ou
 }
 extern "C" int mi355_qmatmul_ref(float* out, const float* x, const void* w_native, int32_t ggml_type, int32_t T,
                                  int32_t N, int32_t K, int64_t stream) {
-    if ((ggml_type != MI355_GGML_Q4_K && ggml_type != MI355_GGML_Q6_K) || (K % 256) || T < 0 || N <= 0) return (int)hipErrorInvalidValue;
+    if (!is_kquant(ggml_type) || (K % 256) || T < 0 || N <= 0) return (int)hipErrorInvalidValue;
     if (T == 0) return 0;
     const int64_t waves = (int64_t)T * N;
     hipLaunchKernelGGL(qmatmul_ref_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, to_stream(stream), out, x,
@@ -2159,6 +2194,7 @@ static int q8_0_launch(const QmmArgs& a, hipStream_t st) {
 
 // ---- parity mode 2 (tests only; kernel in qmm_exact.inc): switch + launcher
 static int g_qmm_exact = 0;
+#include "qmm_q5k.inc"     // Q5_K: its own decode and 9..32-token kernels + launcher (q5k_route)
 extern "C" void mi355_internal_qmm_set_exact(int32_t on) {
     g_qmm_exact = on ? 1 : 0;
     // an exact launch stages no activation image for its successor: forget every chain hint, in both directions of the switch
@@ -2211,6 +2247,8 @@ int mi355_qmm_launch(QmmArgs a, int64_t stream) {
     if (a.nseg >= 1 && a.seg[0].type == MI355_GGML_Q8_0) return q8_0_launch(a, to_stream(stream));
     if (a.K <= 0 || (a.K % 256) || a.B < 0 || a.nseg < 1 || a.nseg > 3) return (int)hipErrorInvalidValue;
     if (a.B == 0) return 0;
+    for (int s = 0; s < a.nseg; ++s)                            // any Q5_K segment: the launch belongs to qmm_q5k.inc, whatever else it asks for
+        if (a.seg[s].type == MI355_GGML_Q5_K) return q5k_route(a, to_stream(stream));
     for (int s = 0; s < a.nseg; ++s)
         if (a.seg[s].type != MI355_GGML_Q4_K && a.seg[s].type != MI355_GGML_Q6_K) return (int)hipErrorInvalidValue;
     if (a.paired && (a.nseg != 2 || a.seg[0].n_tiles != a.seg[1].n_tiles)) return (int)hipErrorInvalidValue;

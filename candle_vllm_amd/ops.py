@@ -23,7 +23,7 @@ from ._lib import lib, QmmDesc
 
 DT_F32, DT_F16, DT_BF16, DT_U8 = 0, 1, 2, 3
 KV_FLASH, KV_PAGED = 0, 1
-GGML_Q4_K, GGML_Q6_K = 12, 14
+GGML_Q4_K, GGML_Q5_K, GGML_Q6_K = 12, 13, 14
 EPI_STORE, EPI_RESID, EPI_SILU_MUL, EPI_QKV_ROPE_CACHE = 0, 1, 2, 3
 SWAP_H2D, SWAP_D2H, SWAP_D2D = 0, 1, 2
 

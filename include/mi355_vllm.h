@@ -38,6 +38,7 @@ extern "C" {
 #define MI355_KV_PAGED_FP8 2 /* the same with 1-byte OCP e4m3fn elements (x = 16): `--kvcache-dtype fp8` (host layers) */
 /* ggml tensor type ids (GGUF) */
 #define MI355_GGML_Q4_K 12
+#define MI355_GGML_Q5_K 13     /* 176-byte blocks; kernels of its own (csrc/qmm_q5k.inc) */
 #define MI355_GGML_Q6_K 14
 #define MI355_GGML_Q8_0 8      /* TP shards the reference re-quantises (quantized_var_builder.rs:234-269); native blocks, no repack */
 /* swap directions */
@@ -203,7 +204,8 @@ int mi355_qmatmul_ref(float* out, const float* x, const void* w_native, int32_t 
                       int32_t n, int32_t k, int64_t stream);
 
 /* One-time (load-time) re-tiling of a GGUF matrix [n_rows, k] into the MI355X tile order consumed by
- * mi355_qmatmul / mi355_qmatmul_fused.  HOST -> HOST; same byte count per weight; rows padded to 16. */
+ * mi355_qmatmul / mi355_qmatmul_fused.  HOST -> HOST; same byte count per weight; rows padded to 16.  Q4_K, Q5_K, Q6_K
+ * (16-row x 256-k tiles of 2304 / 2816 / 3360 bytes); -1 / hipErrorInvalidValue for any other type or k % 256 != 0. */
 int64_t mi355_qweight_repacked_size(int32_t ggml_type, int64_t n_rows, int64_t k);
 int mi355_qweight_repack(void* dst_host, const void* src_native_host, int32_t ggml_type, int64_t n_rows, int64_t k);
 
@@ -271,6 +273,9 @@ typedef struct mi355_qmm_desc {
      * call is refused (hipErrorNotSupported) and the caller runs the groups one by one. */
     const int32_t* group_block_table;
 } mi355_qmm_desc;
+/* Types per segment: Q4_K, Q5_K, Q6_K in any mix (Q8_0: one segment, STORE / RESID).  A descriptor with a Q5_K segment runs on
+ * kernels of its own and is refused with hipErrorNotSupported (801), nothing computed, when it carries moe_expert_ids,
+ * group_count > 1 or group_block_table; it takes no chain hint (chain_next is ignored). */
 int mi355_qmatmul_fused(const mi355_qmm_desc* desc, int64_t stream);
 /* MoE routing on the device (MlpOrMoe::forward, quantized_llama.rs:56-123, without the host round trip):
  * logits = gate_inp . rms_norm(x) ; softmax ; top-k (descending, ties -> lower expert id, as the stable sort there);
@@ -804,13 +809,16 @@ const void* mi355_gguf_tensor_data(void* gguf, int32_t i);
 int64_t mi355_gguf_tensor_shard(void* gguf, int32_t i, int32_t dim, int32_t rank, int32_t world, void* out, int64_t out_cap);
 /* the fallback of `get_sharded_no_shape` (quantized_var_builder.rs:234-269) for a dim-1 shard that cuts a quantisation block:
  * dequantise to f16, narrow to this rank's columns, re-quantise to Q8_0 (f16 d, 32 x i8 per 34-byte block); the mat-mul of such
- * a tensor goes through the Q8_0 arm of mi355_qmatmul_fused (MI355_GGML_Q8_0, native blocks, no repack).  Q4_K / Q6_K sources */
+ * a tensor goes through the Q8_0 arm of mi355_qmatmul_fused (MI355_GGML_Q8_0, native blocks, no repack).  Q4_K / Q6_K sources
+ * only: a dim-1 shard that cuts a Q5_K block is refused (-2 here, 801 from the loader). */
 int64_t mi355_gguf_tensor_shard_q8_0(void* gguf, int32_t tensor, int32_t rank, int32_t world, void* out, int64_t out_cap);
 /* rows [row0, row0 + n_rows) of a 2-D tensor in the file's block format; rows beyond the tensor are ZERO blocks (rows of 0.0): the
  * vocab-parallel lm_head shard of a padded vocabulary (distributed.rs:1596-1616).  Byte count (out == NULL: size query), -1 / -3 as above. */
 int64_t mi355_gguf_tensor_rows_padded(void* gguf, int32_t tensor, int64_t row0, int64_t n_rows, void* out, int64_t out_cap);
 /* GGUFLLaMa::from_gguf (quantized_llama.rs:203-420): config from the metadata, every tensor handed to the model
- * (matrices Q4_K / Q6_K re-tiled, token_embd dequantised on the device, norms F32).  *model_out = mi355_llama handle. */
+ * (matrices Q4_K / Q5_K / Q6_K re-tiled, token_embd dequantised on the device, norms F32).  *model_out = mi355_llama handle.
+ * Refused with 801 (hipErrorNotSupported): Mixtral expert tensors in Q5_K (the expert kernels decode Q4_K / Q6_K), and a
+ * tensor-parallel dim-1 shard that cuts a Q5_K block (the Q8_0 restatement covers Q4_K / Q6_K). */
 int mi355_llama_load_gguf(const char* path, int32_t max_batch, int32_t max_blocks_per_seq, int32_t block_size,
                           int32_t kv_layout, int32_t max_seq, void** model_out, mi355_llama_config* cfg_out);
 /* The same under tensor parallelism (quantized_llama.rs:316-371, attention.rs:790-848, distributed.rs:1574-1629): rank
@@ -825,7 +833,7 @@ int mi355_llama_load_gguf_tp(const char* path, int32_t max_batch, int32_t max_bl
                              int32_t kv_layout, int32_t max_seq, int32_t tp_rank, int32_t tp_world, void** model_out,
                              mi355_llama_config* cfg_out);
 /* Host-only dry run of the loader (no device call): reads the metadata, checks every tensor the model needs against it
- * (present, Q4_K / Q6_K or F32 where required, shapes [rows, cols] consistent with head counts / embedding length / feed
+ * (present, Q4_K / Q5_K / Q6_K or F32 where required; Q5_K expert tensors and Q5_K dim-1 shards that cut a block: 801, shapes [rows, cols] consistent with head counts / embedding length / feed
  * forward length / vocabulary, tile- and block-aligned, shardable `tp_world` ways) and fills cfg_out with the GLOBAL
  * dimensions.  0 = mi355_llama_load_gguf[_tp] will accept the file; hipErrorInvalidValue (1) = malformed / inconsistent;
  * hipErrorNotSupported (801) = a format or shard this build does not serve (other ggml types, re-quantising shards).
