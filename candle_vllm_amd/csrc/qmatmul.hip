@@ -1845,7 +1845,7 @@ static int qpg_launch(const QmmArgs& a0, hipStream_t st) {
     QmmArgs a = a0;
     a.paired = 0;
     for (int s = 0; s < a.nseg; ++s)
-        if (a.seg[s].type != MI355_GGML_Q4_K && a.seg[s].type != MI355_GGML_Q6_K) return (int)hipErrorNotSupported;
+        if (!is_kquant(a.seg[s].type) || (a.seg[s].type == MI355_GGML_Q5_K && a.blk_tab)) return (int)hipErrorNotSupported;
     if (a.moe_expert || (a.K & 255)) return (int)hipErrorNotSupported;
     int n_slots = 0;
     for (int s = 0; s < a.nseg; ++s) n_slots += a.seg[s].n_tiles;
@@ -1871,6 +1871,9 @@ static int qpg_launch(const QmmArgs& a0, hipStream_t st) {
         (void)hipFuncSetAttribute((const void*)qpg_gemm_lds2_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
         (void)hipFuncSetAttribute((const void*)qpg_gemm_lds2_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
         (void)hipFuncSetAttribute((const void*)qpg_gemm_lds2_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
+        (void)hipFuncSetAttribute((const void*)qpg_gemm_kernel<MI355_GGML_Q5_K, 4, 2, 1, 8, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
+        (void)hipFuncSetAttribute((const void*)qpg_gemm_lds2_kernel<true, false, MI355_GGML_Q5_K>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
+        (void)hipFuncSetAttribute((const void*)qpg_gemm_lds2_kernel<false, false, MI355_GGML_Q5_K>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
         (void)hipFuncSetAttribute((const void*)qpg_gemm_q6k_kernel<2, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
         (void)hipFuncSetAttribute((const void*)qpg_gemm_q6k_lds_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         (void)hipFuncSetAttribute((const void*)qpg_gemm_q6k_lds_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
@@ -1879,19 +1882,20 @@ static int qpg_launch(const QmmArgs& a0, hipStream_t st) {
         attr_done.set();
     }
     hipLaunchKernelGGL(qpg_rowprep_kernel, dim3(Tpad), dim3(256), 0, st, a, im);          // row statistics + image, one launch (workgroup = token)
-    // mi355_set_tuning(48, 1), the default: all segments Q4_K, one activation plane, and an epilogue that is a store / residual add /
-    // SiLU * up over two equal segments -> the GEMM writes the outputs itself, no C buffer, no epilogue launch
+    // mi355_set_tuning(48, 1), the default: all segments Q4_K (or all Q5_K), one activation plane, and an epilogue that is a store /
+    // residual add / SiLU * up over two equal segments -> the GEMM writes the outputs itself, no C buffer, no epilogue launch
     {
-        bool all_q4 = true;
-        for (int s = 0; s < a.nseg; ++s) all_q4 = all_q4 && a.seg[s].type == MI355_GGML_Q4_K;
+        bool all_q4 = true, all_q5 = true;
+        for (int s = 0; s < a.nseg; ++s) { all_q4 = all_q4 && a.seg[s].type == MI355_GGML_Q4_K; all_q5 = all_q5 && a.seg[s].type == MI355_GGML_Q5_K; }
         const bool epi_ok = a.epi == MI355_EPI_STORE || a.epi == MI355_EPI_RESID ||
                             (a.epi == MI355_EPI_SILU_MUL && a.nseg == 2 && a.seg[0].n_tiles == a.seg[1].n_tiles && a.seg[0].n_rows == a.seg[1].n_rows);
-        if (g_tune_qpg_fepi && all_q4 && epi_ok && parts == 1) {
+        if (g_tune_qpg_fepi && (all_q4 || all_q5) && epi_ok && parts == 1) {
             QmmArgs r = a;
             r.norm_w = nullptr;                                 // applied while the image was built
             // 64 tokens x 256 rows per workgroup (waves 64 x 32), two workgroups per CU
             const dim3 g_(Tpad / 64, (n_slots + 15) / 16), b_(512);
-            if (a.blk_tab) hipLaunchKernelGGL((qpg_gemm_lds2_kernel<true, true>), g_, b_, (size_t)QPG2_BYTES, st, r, im, C, ldp, n_slots, 0);
+            if (all_q5) hipLaunchKernelGGL((qpg_gemm_lds2_kernel<true, false, MI355_GGML_Q5_K>), g_, b_, (size_t)QPG5_BYTES, st, r, im, C, ldp, n_slots, 0);
+            else if (a.blk_tab) hipLaunchKernelGGL((qpg_gemm_lds2_kernel<true, true>), g_, b_, (size_t)QPG2_BYTES, st, r, im, C, ldp, n_slots, 0);
             else hipLaunchKernelGGL((qpg_gemm_lds2_kernel<true>), g_, b_, (size_t)QPG2_BYTES, st, r, im, C, ldp, n_slots, 0);
             return (int)hipGetLastError();
         }
@@ -1908,7 +1912,7 @@ static int qpg_launch(const QmmArgs& a0, hipStream_t st) {
             return (int)hipErrorNotSupported;
         }
     }
-    // q | k | v of a prompt step (EPI_QKV_ROPE_CACHE, round 6): q and k (Q4_K) -- and v where it is Q4_K too -- go through the fused store loop
+    // q | k | v of a prompt step (EPI_QKV_ROPE_CACHE, round 6): q and k (both Q4_K or both Q5_K) -- and v where it has their type -- go through the fused store loop
     // (RoPE + bf16 + cache scatter in the GEMM); a Q6_K v (half the layers of a Q4_K_M file) keeps its own GEMM + the epilogue launch, which
     // then sees q and k as empty segments (n_rows = 0: their columns of C were never written)
 #ifndef QPG_FUSE_Q6K
@@ -1922,14 +1926,18 @@ static int qpg_launch(const QmmArgs& a0, hipStream_t st) {
 #endif
     // (from 1024 tokens: measured +0.7 % at 2048 and +1.2 % at 4096 tokens, -1.9 % at 512 -- profiles/r06_prompt_qkv_fused_ab.txt)
     if (QPG_FUSE_QKV && T >= 1024 && g_tune_qpg_fepi && parts == 1 && a.epi == MI355_EPI_QKV_ROPE_CACHE && a.nseg == 3 &&
-        a.seg[0].type == MI355_GGML_Q4_K && a.seg[1].type == MI355_GGML_Q4_K && (QPG_FUSE_Q6K || a.seg[2].type == MI355_GGML_Q4_K)) {
-        const bool v4 = a.seg[2].type == MI355_GGML_Q4_K;
+        a.seg[0].type != MI355_GGML_Q6_K && a.seg[1].type == a.seg[0].type &&
+        (a.seg[2].type == a.seg[0].type || (QPG_FUSE_Q6K && a.seg[2].type == MI355_GGML_Q6_K))) {
+        const bool v4 = a.seg[2].type == a.seg[0].type;                 // v goes with q and k
+        const bool q5 = a.seg[0].type == MI355_GGML_Q5_K;
         QmmArgs r = a;
         r.norm_w = nullptr;                                         // applied while the image was built
         if (!v4) r.nseg = 2;
         int f_slots = 0;
         for (int q = 0; q < r.nseg; ++q) f_slots += r.seg[q].n_tiles;
-        hipLaunchKernelGGL((qpg_gemm_lds2_kernel<true>), dim3(Tpad / 64, (f_slots + 15) / 16), dim3(512), (size_t)QPG2_BYTES, st, r, im, C, ldp, f_slots, 0);
+        const dim3 gf(Tpad / 64, (f_slots + 15) / 16);
+        if (q5) hipLaunchKernelGGL((qpg_gemm_lds2_kernel<true, false, MI355_GGML_Q5_K>), gf, dim3(512), (size_t)QPG5_BYTES, st, r, im, C, ldp, f_slots, 0);
+        else hipLaunchKernelGGL((qpg_gemm_lds2_kernel<true>), gf, dim3(512), (size_t)QPG2_BYTES, st, r, im, C, ldp, f_slots, 0);
         if (v4) return (int)hipGetLastError();
         // v (Q6_K): its own GEMM with the fused store loop; q and k stay in the descriptor as EMPTY segments (no tiles) so that the value
         // segment keeps its role (2 = v: bf16 + cache scatter, no rotation) and its row offsets
@@ -1958,6 +1966,12 @@ static int qpg_launch(const QmmArgs& a0, hipStream_t st) {
                 hipLaunchKernelGGL((qpg_gemm_lds2_kernel<false>), g4, b_, (size_t)QPG2_BYTES, st, r, im, C, ldp, run_slots, slot_base);
             else                                                        // hi + lo planes ("exact" activations): the register-fed form
                 hipLaunchKernelGGL((qpg_gemm_kernel<MI355_GGML_Q4_K, 4, 2, 1, 8, 2>), g4, b_, (size_t)2 * 2 * 64 * QPG_ROWB, st, r, im, C, ldp, run_slots, slot_base);
+        } else if (r.seg[0].type == MI355_GGML_Q5_K) {                  // the same two kernels over Q5_K tiles
+            const dim3 g5(Tpad / 64, (run_slots + 15) / 16), b_(512);
+            if (parts == 1)
+                hipLaunchKernelGGL((qpg_gemm_lds2_kernel<false, false, MI355_GGML_Q5_K>), g5, b_, (size_t)QPG5_BYTES, st, r, im, C, ldp, run_slots, slot_base);
+            else
+                hipLaunchKernelGGL((qpg_gemm_kernel<MI355_GGML_Q5_K, 4, 2, 1, 8, 2>), g5, b_, (size_t)2 * 2 * 64 * QPG_ROWB, st, r, im, C, ldp, run_slots, slot_base);
         } else {
             if (parts == 1) {                      // Q6_K: 64 tokens x 256 rows per workgroup; token blocks fastest
                 const dim3 grid(Tpad / 64, (run_slots + 15) / 16);

@@ -21,6 +21,7 @@
 typedef _Float16 qpg_h2 __attribute__((ext_vector_type(2)));
 typedef _Float16 qpg_h4 __attribute__((ext_vector_type(4)));
 typedef _Float16 qpg_h8 __attribute__((ext_vector_type(8)));
+typedef unsigned int qpg_u32x2 __attribute__((ext_vector_type(2)));
 
 #define QPG_BM 128
 #define QPG_BN 128
@@ -191,6 +192,50 @@ __device__ __forceinline__ qpg_h8 qpg_frag_q4k_p(uint32_t w0, uint32_t w0s, uint
     return qpg_h8{r0[0], r0[1], r1[0], r1[1], r2[0], r2[1], r3[0], r3[1]};
 }
 
+// ---- Q5_K (tile: mi355_qweight_repack): the Q4_K nibble planes plus the lane's 64 fifth bits, transposed so that the fifth bits of the
+// element pair (c, c + 2) of sub-block j sit at bits n and n + 16 of a word, n = 2j + c: ONE shift and ONE AND with `mask` = (1 << pos) twice
+// put them at bit `pos` of both 16-bit halves of an operand dword.
+__device__ __forceinline__ uint32_t qpg_q5k_hbits(uint32_t h, const int n, const int pos, const uint32_t mask) {
+    return (n >= pos ? (h >> (n - pos)) : (h << (pos - n))) & mask;
+}
+
+// B fragment of sub-block j of a Q5_K tile for the register-fed kernel, as qpg_frag_q4k: code 0x6400 | nibble | fifth bit << 4 = 1024 + q
+// (q <= 31), fma(1024 + q, s, -1024 s) = s q <= 63 * 31 = 1953 < 2048: an exact f16 integer.  `h0, h1` = the lane's fifth-bit words
+// (elements 0..3 / 4..7), B = 0x00100010 in a VGPR.
+__device__ __forceinline__ qpg_h8 qpg_frag_q5k(uint32_t w0, uint32_t w1, uint32_t h0, uint32_t h1, const int j, const uint32_t sc, const uint32_t M,
+                                               const uint32_t B, const uint32_t C) {
+    const qpg_h2 K1024 = {(_Float16)1024.f, (_Float16)1024.f};
+    const qpg_h2 S = __builtin_bit_cast(qpg_h2, (sc | (sc << 16)) | C) - K1024;
+    const qpg_h2 OFF = S * qpg_h2{(_Float16)(-1024.f), (_Float16)(-1024.f)};
+    const int sh = (j & 1) ? 4 : 0;
+    const qpg_h2 a02 = __builtin_bit_cast(qpg_h2, ((w0 >> sh) & M) | (qpg_q5k_hbits(h0, 2 * j, 4, B) | C));
+    const qpg_h2 a13 = __builtin_bit_cast(qpg_h2, ((w0 >> (sh + 8)) & M) | (qpg_q5k_hbits(h0, 2 * j + 1, 4, B) | C));
+    const qpg_h2 b02 = __builtin_bit_cast(qpg_h2, ((w1 >> sh) & M) | (qpg_q5k_hbits(h1, 2 * j, 4, B) | C));
+    const qpg_h2 b13 = __builtin_bit_cast(qpg_h2, ((w1 >> (sh + 8)) & M) | (qpg_q5k_hbits(h1, 2 * j + 1, 4, B) | C));
+    const qpg_h2 r0 = __builtin_elementwise_fma(a02, S, OFF), r1 = __builtin_elementwise_fma(a13, S, OFF);
+    const qpg_h2 r2 = __builtin_elementwise_fma(b02, S, OFF), r3 = __builtin_elementwise_fma(b13, S, OFF);
+    return qpg_h8{r0[0], r0[1], r1[0], r1[1], r2[0], r2[1], r3[0], r3[1]};
+}
+
+// The same for the LDS-fed kernel, nibbles taken where they stand as in qpg_frag_q4k_p.  Low nibbles (j even): 0x6400 | nibble | fifth bit
+// << 4 = 1024 + q, offset -1024 s.  High nibbles (j odd): the fifth bit goes to bit 8 of each half and the exponent pattern is 0x5400
+// (64.0, whose mantissa ulp is 1/16): 0x5400 | nibble << 4 | bit << 8 = 64 + q, offset -64 s -- the SAME scale operand s serves both, and
+// (64 + q) s - 64 s = s q <= 1953 is exact behind the fma's single rounding.  `mk` / `bk` / `C` = 0x000F000F / 0x00100010 / 0x64006400
+// (j even) or 0x00F000F0 / 0x01000100 / 0x54005400 (j odd): masks in SGPRs, `C` in a VGPR.  The offset is one packed multiply per fragment: the Q4_K arm keeps
+// s, s / 16 and both offsets of every sub-block in 32 registers, which next to the fifth-bit words would cost the fourth wave per SIMD.
+__device__ __forceinline__ qpg_h8 qpg_frag_q5k_p(uint32_t w0, uint32_t w0s, uint32_t w1, uint32_t w1s, uint32_t h0, uint32_t h1, const int j,
+                                                 const qpg_h2 sp, const int e, const uint32_t mk, const uint32_t bk, const uint32_t C) {
+    const qpg_h2 S = e ? __builtin_shufflevector(sp, sp, 1, 1) : __builtin_shufflevector(sp, sp, 0, 0);
+    const _Float16 ko = (j & 1) ? (_Float16)(-64.f) : (_Float16)(-1024.f);
+    const qpg_h2 OFF = S * qpg_h2{ko, ko};
+    const int pos = (j & 1) ? 8 : 4;
+    const qpg_h2 r0 = __builtin_elementwise_fma(__builtin_bit_cast(qpg_h2, (w0 & mk) | (qpg_q5k_hbits(h0, 2 * j, pos, bk) | C)), S, OFF);
+    const qpg_h2 r1 = __builtin_elementwise_fma(__builtin_bit_cast(qpg_h2, (w0s & mk) | (qpg_q5k_hbits(h0, 2 * j + 1, pos, bk) | C)), S, OFF);
+    const qpg_h2 r2 = __builtin_elementwise_fma(__builtin_bit_cast(qpg_h2, (w1 & mk) | (qpg_q5k_hbits(h1, 2 * j, pos, bk) | C)), S, OFF);
+    const qpg_h2 r3 = __builtin_elementwise_fma(__builtin_bit_cast(qpg_h2, (w1s & mk) | (qpg_q5k_hbits(h1, 2 * j + 1, pos, bk) | C)), S, OFF);
+    return qpg_h8{r0[0], r0[1], r1[0], r1[1], r2[0], r2[1], r3[0], r3[1]};
+}
+
 // Workgroup = 4 waves as 2 (M) x 2 (N), one wave per SIMD with the whole 512-register file (the 8-wave version of this
 // kernel spilled its activation prefetch at 256 VGPRs and sat at 15 % MFMA-busy): wave tile 64 tokens x 64 rows.
 // Register plan: y 64 + acc 64 (per-k-block accumulators), quantised tiles 64 (header, next header, plane 0, plane 1 of
@@ -202,11 +247,14 @@ __device__ __forceinline__ qpg_h8 qpg_frag_q4k_p(uint32_t w0, uint32_t w0s, uint
 // MFMAs or the unpack it is not shorter at all): a wider workgroup tile in N re-reads the image less often, a wider wave
 // tile in N reads each A fragment from LDS less often.
 // The register-fed form: since round 4 it runs only for hi + lo activation planes ("exact" activations, PARTS = 2); one plane takes
-// qpg_gemm_lds2_kernel below.
+// qpg_gemm_lds2_kernel below.  WT = MI355_GGML_Q5_K: tile stride Q5K_TILE, the lane's two fifth-bit words travel with the headers (one
+// k-block ahead), qpg_frag_q5k builds the fragment (hipcc, gfx950, -O3, <Q5_K, 4, 2, 1, 8, 2>: 218 VGPRs and the Q4_K instantiation's 48 B of scratch).
 template <int WT, int MTW, int NTW, int WM, int WN, int PARTS>
 __global__ void __launch_bounds__(WM * WN * 64, 1) qpg_gemm_kernel(const QmmArgs a, const QpgImg im, float* __restrict__ C, const int ldc,
                                                           const int n_slots, const int slot_base) {
-    static_assert(WT == MI355_GGML_Q4_K, "Q6_K goes through qpg_gemm_q6k_kernel");
+    static_assert(WT == MI355_GGML_Q4_K || WT == MI355_GGML_Q5_K, "Q6_K goes through qpg_gemm_q6k_kernel");
+    constexpr bool Q5 = WT == MI355_GGML_Q5_K;
+    constexpr int TILEB = Q5 ? Q5K_TILE : Q4K_TILE;
     extern __shared__ __attribute__((aligned(1024))) uint8_t smem[];  // A tile: [2 buffers][2 parts][128 rows][128 B]
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     constexpr int NTHR = WM * WN * 64, BMk = 16 * MTW * WM, SLOTS = NTW * WN;   // threads, token rows and row tiles per workgroup
@@ -231,16 +279,20 @@ __global__ void __launch_bounds__(WM * WN * 64, 1) qpg_gemm_kernel(const QmmArgs
         if (!have[i]) slot = 0;
         int t = slot, sg = 0;
         while (sg + 1 < a.nseg && t >= a.seg[sg].n_tiles) { t -= a.seg[sg].n_tiles; ++sg; }
-        wbase[i] = a.seg[sg].w + (size_t)t * nkb * Q4K_TILE;
+        wbase[i] = a.seg[sg].w + (size_t)t * nkb * TILEB;
     }
     uint4 hdr[NTW], hdrn[NTW], p0[NTW], p1[NTW];
-    auto ld_hdr = [&](int kb, uint4 (&H)[NTW]) {
+    qpg_u32x2 hq[NTW], hqn[NTW];                                      // Q5_K: fifth-bit words of this / the next k-block
+    auto ld_hdr = [&](int kb, uint4 (&H)[NTW], qpg_u32x2 (&Q)[NTW]) {
 #pragma unroll
-        for (int i = 0; i < NTW; ++i) H[i] = ld_nt16(reinterpret_cast<const uint4*>(wbase[i] + (size_t)kb * Q4K_TILE) + n16);
+        for (int i = 0; i < NTW; ++i) {
+            H[i] = ld_nt16(reinterpret_cast<const uint4*>(wbase[i] + (size_t)kb * TILEB) + n16);
+            if constexpr (Q5) Q[i] = __builtin_nontemporal_load(reinterpret_cast<const qpg_u32x2*>(wbase[i] + (size_t)kb * TILEB + 2304) + lane);
+        }
     };
     auto ld_plane = [&](int kb, int p, uint4 (&P)[NTW]) {
 #pragma unroll
-        for (int i = 0; i < NTW; ++i) P[i] = ld_nt16(reinterpret_cast<const uint4*>(wbase[i] + (size_t)kb * Q4K_TILE) + 16 + 64 * p + lane);
+        for (int i = 0; i < NTW; ++i) P[i] = ld_nt16(reinterpret_cast<const uint4*>(wbase[i] + (size_t)kb * TILEB) + 16 + 64 * p + lane);
     };
     // ---- activation tile: global image (already in LDS order) -> registers -> LDS; 32 KB per chunk = 4 x 16 B per thread
     const size_t part_stride = (size_t)im.Tpad * QPG_ROWB;
@@ -267,9 +319,11 @@ __global__ void __launch_bounds__(WM * WN * 64, 1) qpg_gemm_kernel(const QmmArgs
         for (int nt = 0; nt < NTW; ++nt) { y[mt][nt] = f32x4_t{0.f, 0.f, 0.f, 0.f}; acc[mt][nt] = f32x4_t{0.f, 0.f, 0.f, 0.f}; }
     uint32_t Mk = 0x000F000Fu, Ck = 0x64006400u;
     asm volatile("" : "+v"(Mk), "+v"(Ck));
+    uint32_t Bk = 0x00100010u;
+    if constexpr (Q5) asm volatile("" : "+v"(Bk));
 
     uint4 xa_[XU];                                                      // activation chunk kc+1 in flight
-    ld_hdr(0, hdr); ld_plane(0, 0, p0); ld_plane(0, 1, p1);
+    ld_hdr(0, hdr, hq); ld_plane(0, 0, p0); ld_plane(0, 1, p1);
     x_load(0, xa_);
     x_store(0, xa_);
     __syncthreads();
@@ -307,13 +361,14 @@ __global__ void __launch_bounds__(WM * WN * 64, 1) qpg_gemm_kernel(const QmmArgs
                 const uint32_t w0 = (c & 1) ? pl.z : pl.x, w1 = (c & 1) ? pl.w : pl.y;
                 const uint32_t s0 = hdr[nt].y, s2 = hdr[nt].w;
                 const uint32_t scw = (j < 4) ? (s0 & 0x3F3F3F3Fu) : ((s2 & 0x0F0F0F0Fu) | ((s0 >> 2) & 0x30303030u));
-                bf[nt] = qpg_frag_q4k(w0, w1, h, (scw >> (8 * (j & 3))) & 0xFFu, Mk, Ck);
+                if constexpr (Q5) bf[nt] = qpg_frag_q5k(w0, w1, hq[nt].x, hq[nt].y, j, (scw >> (8 * (j & 3))) & 0xFFu, Mk, Bk, Ck);
+                else bf[nt] = qpg_frag_q4k(w0, w1, h, (scw >> (8 * (j & 3))) & 0xFFu, Mk, Ck);
             }
             if (h == 1) {
                 // the plane's last sub-block is unpacked: its registers take the NEXT k-block's bytes (>= 2 chunks ahead of use)
                 if (c == 1 && kb + 1 < nkb) ld_plane(kb + 1, 0, p0);
                 if (c == 3 && kb + 1 < nkb) ld_plane(kb + 1, 1, p1);
-                if (c == 2 && kb + 1 < nkb) ld_hdr(kb + 1, hdrn);
+                if (c == 2 && kb + 1 < nkb) ld_hdr(kb + 1, hdrn, hqn);
             }
             // (3) MFMAs: the hi (and lo) part of the m-tiles against the four B fragments (independent accumulators per tile pair)
 #pragma unroll
@@ -353,7 +408,7 @@ __global__ void __launch_bounds__(WM * WN * 64, 1) qpg_gemm_kernel(const QmmArgs
                 }
             }
 #pragma unroll
-            for (int nt = 0; nt < NTW; ++nt) hdr[nt] = hdrn[nt];
+            for (int nt = 0; nt < NTW; ++nt) { hdr[nt] = hdrn[nt]; hq[nt] = hqn[nt]; }
         }
         if (kc + 1 < nchunk) x_store(buf_next, xa_);
         __syncthreads();                                              // buffer of kc+1 is complete, buffer of kc is free again
@@ -574,9 +629,33 @@ __global__ void __launch_bounds__(512, 1) qpg_gemm_q6k_kernel(const QmmArgs a, c
 #define QPG2_BYTES (QPG2_IMG + QPG2_PLANES + 2 * QPG2_HS)
 #define QPG2_NE 1                              // vmcnt in front of the barrier of chunks 0 and 2
 #define QPG2_NO 8                              // ... of chunks 1 and 3
-template <bool FEPI, bool TAB = false>
-__global__ void __launch_bounds__(512, 2) qpg_gemm_lds2_kernel(const QmmArgs a, const QpgImg im, float* __restrict__ C, const int ldc,
+// ---- WT = MI355_GGML_Q5_K: the same kernel over Q5_K tiles (2816 B: header and nibble planes at the Q4_K offsets, then 8 B of transposed
+// fifth bits per lane).  One more DMA per wave and k-block, Q, brings the fifth-bit words of BOTH tiles (lanes 0..31: the 512 B of tile 0,
+// lanes 32..63: of tile 1) into one contiguous KiB; the wave copies them into registers (2 dwords per tile) where it reads the headers, at
+// chunk 0.  The fragment is qpg_frag_q5k_p: one shift and one and-or per operand dword on top of the Q4_K unpack; scales, mins, d, dmin,
+// the accumulator chain and the minimum term are the Q4_K arm's.
+// LDS, 80 KiB = half a CU exactly, so that two workgroups still fit: image ring 32 KiB | planes, one stage, 32 KiB | fifth-bit words, ONE
+// stage, 8 KiB | headers, ONE stage, 4 KiB | sums, two stages of 2 KiB.  Headers and fifth-bit words are private to their wave and sit in
+// its registers from chunk 0 on: their region takes the next k-block's in chunk 2 of the same k-block (the planes' rule).  The sums are
+// read by every wave in chunk 3 and keep two stages.
+// VMEM order per wave and k-block:  I P1 P1 | I | I H Q S P0 P0 | I ; prologue  I(0) | I(1) H Q S P0 P0 | I(2) : 7 weight DMAs, all but 1
+// landed in front of an even chunk's barrier, all but 9 in front of an odd one's (tests/test_cpu_q5k_dma_plan.py).
+// hipcc, gfx950, -O3: 125 VGPRs (FEPI) / 124, no scratch, 4 waves per SIMD (Q4_K: 125); hipOccupancyMaxActiveBlocksPerMultiprocessor: 2.
+#define QPG5_Q (8 * 1024)                      // fifth-bit words: 8 waves x 2 tiles x 512 B
+#define QPG5_H 4096                            // headers: 8 waves x 2 tiles x 256 B
+#define QPG5_S 2048                            // one stage of sums: 64 tokens x 32 B
+#define QPG5_BYTES (QPG2_IMG + QPG2_PLANES + QPG5_Q + QPG5_H + 2 * QPG5_S)
+#define QPG5_NW 7                              // weight DMA instructions per wave and k-block
+#define QPG5_NE 1                              // vmcnt in front of the barrier of chunks 0 and 2
+#define QPG5_NO 9                              // ... of chunks 1 and 3
+static_assert(QPG5_BYTES == 80 * 1024, "two workgroups per CU: 2 x 80 KiB = the CU's 160 KiB");
+// (the Q5_K arm asks for 4 waves per SIMD = 128 VGPRs outright: left at 2, the compiler spent 131..133 and with them the second workgroup)
+template <bool FEPI, bool TAB = false, int WT = MI355_GGML_Q4_K>
+__global__ void __launch_bounds__(512, WT == MI355_GGML_Q5_K ? 4 : 2) qpg_gemm_lds2_kernel(const QmmArgs a, const QpgImg im, float* __restrict__ C, const int ldc,
                                                               const int n_slots, const int slot_base) {
+    static_assert(WT == MI355_GGML_Q4_K || (WT == MI355_GGML_Q5_K && !TAB), "Q6_K: qpg_gemm_q6k_lds_kernel; no block-table launch for Q5_K");
+    constexpr bool Q5 = WT == MI355_GGML_Q5_K;
+    constexpr int TILEB = Q5 ? Q5K_TILE : Q4K_TILE, NE = Q5 ? QPG5_NE : QPG2_NE, NO = Q5 ? QPG5_NO : QPG2_NO;
     constexpr int MTW = 4, NTW = 2, WN = 8, BMk = 64, SLOTS = NTW * WN, CHB = BMk * QPG_ROWB, LEAD = QPG2_LEAD, RING = QPG2_RING;
     extern __shared__ __attribute__((aligned(1024))) uint8_t smem[];
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -628,7 +707,7 @@ __global__ void __launch_bounds__(512, 2) qpg_gemm_lds2_kernel(const QmmArgs a, 
         if (!have[i]) slot = 0;
         int t = slot, sg = 0;
         while (sg + 1 < a.nseg && t >= a.seg[sg].n_tiles) { t -= a.seg[sg].n_tiles; ++sg; }
-        wbase[i] = a.seg[sg].w + e_grp * (size_t)a.moe_stride[sg] + (size_t)t * nkb * Q4K_TILE;
+        wbase[i] = a.seg[sg].w + e_grp * (size_t)a.moe_stride[sg] + (size_t)t * nkb * TILEB;
         e_sg[i] = sg; e_tile[i] = t;
     }
     const uint32_t lds0 = __builtin_amdgcn_readfirstlane((uint32_t)(size_t)(qmg_lptr_t)smem);
@@ -641,11 +720,24 @@ __global__ void __launch_bounds__(512, 2) qpg_gemm_lds2_kernel(const QmmArgs a, 
     auto dma_plane = [&](int kb, int pl) {                            // two instructions (tile 0, tile 1)
 #pragma unroll
         for (int i = 0; i < NTW; ++i)
-            qmg_dma16(wbase[i] + (size_t)kb * Q4K_TILE + 256 + pl * 1024 + lane * 16, lds_pl + (uint32_t)((pl * NTW + i) * 1024));
+            qmg_dma16(wbase[i] + (size_t)kb * TILEB + 256 + pl * 1024 + lane * 16, lds_pl + (uint32_t)((pl * NTW + i) * 1024));
     };
     auto dma_hdr_sums = [&](int kb, int stage) {                      // two instructions: headers of both tiles (32 lanes), this wave's share of the sums (16 lanes)
+        if constexpr (Q5) {                                           // three: H, Q (64 lanes, one stage each), S (two stages)
+            // the per-lane source addresses are formed here, once per k-block, from a lane number the compiler cannot see through: hoisted
+            // out of the loop they are six more VGPRs, which it spilled -- with a full vmcnt(0) behind each reload
+            int ln = lane;
+            asm volatile("" : "+v"(ln));
+            const uint32_t hq = lds0 + QPG2_IMG + QPG2_PLANES;
+            const size_t ko = (size_t)kb * TILEB, w10 = (size_t)(wbase[1] - wbase[0]);      // (tile 1 of this lane = tile 0 + w10, modulo 2^64)
+            if (ln < 32) qmg_dma16(wbase[0] + ((ln & 16) ? w10 : 0) + ko + (ln & 15) * 16, hq + QPG5_Q + (uint32_t)(wave * 512));
+            qmg_dma16(wbase[0] + ((ln & 32) ? w10 : 0) + ko + 2304 + (ln & 31) * 16, hq + (uint32_t)(wave * 1024));   // lanes 0..31: fifth-bit words of tile 0, 32..63: of tile 1
+            if (ln < 16) qmg_dma16(im.sfrag + ((size_t)kb * im.Tpad + t0) * 32 + wave * 256 + ln * 16,
+                                   hq + QPG5_Q + QPG5_H + (uint32_t)(stage * QPG5_S + wave * 256));
+            return;
+        }
         const uint32_t hs = lds0 + QPG2_IMG + QPG2_PLANES + (uint32_t)(stage * QPG2_HS);
-        if (lane < 32) qmg_dma16(hsrc + (size_t)kb * Q4K_TILE, hs + (uint32_t)(wave * 512));
+        if (lane < 32) qmg_dma16(hsrc + (size_t)kb * TILEB, hs + (uint32_t)(wave * 512));
         if (lane < 16) qmg_dma16(im.sfrag + ((size_t)kb * im.Tpad + t0) * 32 + wave * 256 + lane * 16, hs + 4096u + (uint32_t)(wave * 256));
     };
 
@@ -656,6 +748,10 @@ __global__ void __launch_bounds__(512, 2) qpg_gemm_lds2_kernel(const QmmArgs a, 
         for (int nt = 0; nt < NTW; ++nt) { y[mt][nt] = f32x4_t{0.f, 0.f, 0.f, 0.f}; acc[mt][nt] = f32x4_t{0.f, 0.f, 0.f, 0.f}; }
     uint32_t Mk = 0x000F000Fu, Mh = 0x00F000F0u, Ck = 0x64006400u;
     asm volatile("" : "+v"(Mk), "+v"(Mh), "+v"(Ck));
+    // Q5_K: an operand dword is ((h >> n) & B | C) then (w & M | that) -- two v_and_or_b32 with ONE constant each next to a register, so
+    // the masks live in SGPRs and only the exponent patterns (Ck, and Ch = f16 64.0 twice for the high nibbles) take VGPRs
+    uint32_t M5k = 0x000F000Fu, M5h = 0x00F000F0u, B4 = 0x00100010u, B8 = 0x01000100u, Ch = 0x54005400u;
+    if constexpr (Q5) asm volatile("" : "+s"(M5k), "+s"(M5h), "+s"(B4), "+s"(B8), "+v"(Ch));
 
     // prologue in the steady state's order (chunks 1, 2, 3 of a k-block "-1"): I(0) | I(1) H S P0 P0 | I(2)
     dma_image(0, 0);
@@ -677,13 +773,15 @@ __global__ void __launch_bounds__(512, 2) qpg_gemm_lds2_kernel(const QmmArgs a, 
         const int kbn = min(kb + 1, nkb - 1);
         const uint8_t* Wpl = smem + QPG2_IMG + wave * 4096;                              // this wave's planes
         const uint8_t* Whs = smem + QPG2_IMG + QPG2_PLANES + (size_t)(kb & 1) * QPG2_HS;  // headers | sums of this k-block
+        const uint8_t* Wq5 = smem + QPG2_IMG + QPG2_PLANES;                               // Q5_K: fifth-bit words | headers | sums x 2
         uint4 H[NTW], pl[NTW];
+        qpg_u32x2 qh[NTW];                                                 // Q5_K: the lane's fifth-bit words
         qpg_h2 scp[NTW][4], offp[NTW][4], s16p[NTW][4], off16p[NTW][4];    // scale pairs (s0,s2) (s1,s3) (s4,s6) (s5,s7) and what the nibble positions need of them
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
             const int kc = 4 * kb + c;
-            if ((c & 1) == 0) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(QPG2_NE) : "memory");     // chunk + the plane (c = 0: and headers, sums) it starts to use
-            else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(QPG2_NO) : "memory");
+            if ((c & 1) == 0) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NE) : "memory");     // chunk + the plane (c = 0: and headers, sums) it starts to use
+            else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NO) : "memory");
             __syncthreads();                                          // everyone's shares have landed; the previous chunk (and the plane it finished) is read
             dma_image(min(kc + LEAD, nchunk - 1), (kc + LEAD) & (RING - 1));
             if (c == 0) dma_plane(kb, 1);                             // plane 1 of THIS k-block (chunks 2, 3): its region was read last in chunk 3 of kb - 1
@@ -691,7 +789,8 @@ __global__ void __launch_bounds__(512, 2) qpg_gemm_lds2_kernel(const QmmArgs a, 
             if (c == 0) {
 #pragma unroll
                 for (int nt = 0; nt < NTW; ++nt) {
-                    H[nt] = *reinterpret_cast<const uint4*>(Whs + wave * 512 + nt * 256 + n16 * 16);
+                    H[nt] = *reinterpret_cast<const uint4*>((Q5 ? Wq5 + QPG5_Q : Whs) + wave * 512 + nt * 256 + n16 * 16);
+                    if constexpr (Q5) qh[nt] = *reinterpret_cast<const qpg_u32x2*>(Wq5 + wave * 1024 + nt * 512 + lane * 8);
                     const uint32_t s0 = H[nt].y, s2 = H[nt].w;
                     const uint32_t scl4 = s0 & 0x3F3F3F3Fu, sch = (s2 & 0x0F0F0F0Fu) | ((s0 >> 2) & 0x30303030u);
                     const qpg_h2 K1024 = {(_Float16)1024.f, (_Float16)1024.f};
@@ -700,7 +799,7 @@ __global__ void __launch_bounds__(512, 2) qpg_gemm_lds2_kernel(const QmmArgs a, 
                     scp[nt][2] = __builtin_bit_cast(qpg_h2, (sch & 0x00FF00FFu) | Ck) - K1024;
                     scp[nt][3] = __builtin_bit_cast(qpg_h2, ((sch >> 8) & 0x00FF00FFu) | Ck) - K1024;
 #pragma unroll
-                    for (int i = 0; i < 4; ++i) {
+                    for (int i = 0; i < 4; ++i) {                                // (dead code for Q5_K, which needs the scales alone: qpg_frag_q5k_p)
                         offp[nt][i] = scp[nt][i] * qpg_h2{(_Float16)(-1024.f), (_Float16)(-1024.f)};
                         s16p[nt][i] = scp[nt][i] * qpg_h2{(_Float16)0.0625f, (_Float16)0.0625f};
                         off16p[nt][i] = scp[nt][i] * qpg_h2{(_Float16)(-64.f), (_Float16)(-64.f)};
@@ -726,7 +825,10 @@ __global__ void __launch_bounds__(512, 2) qpg_gemm_lds2_kernel(const QmmArgs a, 
                 for (int nt = 0; nt < NTW; ++nt) {
                     const uint32_t w0 = (c & 1) ? pl[nt].z : pl[nt].x, w1 = (c & 1) ? pl[nt].w : pl[nt].y;
                     const int pi = 2 * (j >> 2) + (j & 1), e = (j >> 1) & 1;      // scale pair and element of sub-block j
-                    bf[nt] = qpg_frag_q4k_p(w0, w0 >> 8, w1, w1 >> 8, h ? s16p[nt][pi] : scp[nt][pi], h ? off16p[nt][pi] : offp[nt][pi], e, h ? Mh : Mk, Ck);
+                    if constexpr (Q5)
+                        bf[nt] = qpg_frag_q5k_p(w0, w0 >> 8, w1, w1 >> 8, qh[nt].x, qh[nt].y, j, scp[nt][pi], e, h ? M5h : M5k, h ? B8 : B4, h ? Ch : Ck);
+                    else
+                        bf[nt] = qpg_frag_q4k_p(w0, w0 >> 8, w1, w1 >> 8, h ? s16p[nt][pi] : scp[nt][pi], h ? off16p[nt][pi] : offp[nt][pi], e, h ? Mh : Mk, Ck);
                 }
 #pragma unroll
                 for (int mt = 0; mt < MTW; ++mt)
@@ -738,7 +840,7 @@ __global__ void __launch_bounds__(512, 2) qpg_gemm_lds2_kernel(const QmmArgs a, 
                 // ---- end of the k-block: super-block scale d, then the minimum term  - dmin * sum_j m_j S_j
                 qpg_h4 sa[MTW];
 #pragma unroll
-                for (int mt = 0; mt < MTW; ++mt) sa[mt] = *reinterpret_cast<const qpg_h4*>(Whs + 4096 + (mt * 16 + n16) * 32 + kg * 8);
+                for (int mt = 0; mt < MTW; ++mt) sa[mt] = *reinterpret_cast<const qpg_h4*>((Q5 ? Wq5 + QPG5_Q + QPG5_H - 4096 + (size_t)(kb & 1) * QPG5_S : Whs) + 4096 + (mt * 16 + n16) * 32 + kg * 8);
 #pragma unroll
                 for (int nt = 0; nt < NTW; ++nt) {
                     const float d = f16_bits_to_f32((uint16_t)(H[nt].x & 0xFFFF));
@@ -1088,12 +1190,14 @@ __global__ void __launch_bounds__(512, 1) qpg_gemm_q6k_lds_kernel(const QmmArgs 
 }
 
 // the DMA plan of the LDS-fed prompt kernels for the host-side check of the hand-counted waits (tests/test_cpu_dma_plan.py):
-// kind 2 = qpg_gemm_lds2_kernel (its own instruction order; the two counts are those of the even / odd chunks), 6 = qpg_gemm_q6k_lds_kernel
+// kind 2 = qpg_gemm_lds2_kernel (its own instruction order; the two counts are those of the even / odd chunks), 5 = the same kernel over
+// Q5_K tiles (tests/test_cpu_q5k_dma_plan.py), 6 = qpg_gemm_q6k_lds_kernel
 // ->  {LEAD, RING, image DMAs per wave and chunk, weight DMAs per wave and k-block, vmcnt before chunk 0's barrier, vmcnt before the other
 // chunks' barriers}
 extern "C" int32_t mi355_internal_qpg_dma_plan(int32_t kind, int32_t* out6) {
     if (kind == 6) { const int32_t v[6] = {QPG6_LEAD, QPG6_RING, 1, QPG6_NW, QPG6_N0, QPG6_N1}; for (int i = 0; i < 6; ++i) out6[i] = v[i]; return 0; }
     if (kind == 61) { const int32_t v[6] = {QPG6_LEAD, QPG6_RING, 1, 2 + 3 * 1, QPG6_N0, QPG6_LEAD - 1 + 2 + 3 * 1}; for (int i = 0; i < 6; ++i) out6[i] = v[i]; return 0; }   // NT = 1
     if (kind == 2) { const int32_t v[6] = {QPG2_LEAD, QPG2_RING, 1, 6, QPG2_NE, QPG2_NO}; for (int i = 0; i < 6; ++i) out6[i] = v[i]; return 0; }   // qpg_gemm_lds2_kernel: its own order
+    if (kind == 5) { const int32_t v[6] = {QPG2_LEAD, QPG2_RING, 1, QPG5_NW, QPG5_NE, QPG5_NO}; for (int i = 0; i < 6; ++i) out6[i] = v[i]; return 0; }   // ... over Q5_K tiles
     return -1;
 }

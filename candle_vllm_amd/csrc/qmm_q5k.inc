@@ -7,12 +7,13 @@
 // Tile (mi355_qweight_repack, 2816 B per 16 rows x 256 k): header and nibble planes as the Q4_K tile, then the lane's 64
 // fifth bits transposed into consumption order (layout note next to the repack), so that a code is three bit operations:
 //     (qs >> sh) & 0x000F000F  |  (qh >> (2j + c - 4)) & 0x00100010  |  exponent pattern
-// Two kernels:
+// Prompt steps (>= Q5P_MIN_TOKENS = 192 tokens) take the Q5_K arms of the prompt-step GEMM in qmm_prefill.inc (qpg_gemm_lds2_kernel<., false,
+// MI355_GGML_Q5_K>; hi + lo activation planes: qpg_gemm_kernel<MI355_GGML_Q5_K, ...>) through qpg_launch.  Two kernels here:
 //   * q5k_kernel (1..8 tokens): the streaming mat-vec of the path -- per-wave LDS image of hi + lo bf16 activation rows,
 //     codes 128 + q exact in bf16, the -128 MFMA that cancels the offset and yields the sub-block sums of the minimum
 //     term, d / dmin once per tile, register ring of (k-block, tile) units with a compile-time load count (4 per unit,
 //     5 in launches that mix in Q4_K / Q6_K tiles: those tiles go through compute3_q4k / compute3_q6k), the common epilogue;
-//   * q5g_gemm_kernel (9..32 tokens per launch, longer batches in 32-token chunks): one f16 activation plane with a
+//   * q5g_gemm_kernel (9..32 tokens per launch; 33..191 tokens, and prompts with mi355_set_tuning(6, 0), in 32-token chunks): one f16 activation plane with a
 //     power-of-two scale per (token, k-block) -- the image of qw1_prep_kernel -- B operand sc_j q exact in f16
 //     (63 * 31 = 1953 < 2048), the eight sub-block MFMAs of a k-block chained in one accumulator, the minimum term as one
 //     K = 16 MFMA per m-tile against the staged sub-block sums, d / dmin / 2^e applied per (row, k-block).  Eight waves =
@@ -436,6 +437,11 @@ static int q5k_launch_bt(QmmArgs& a, int R, bool mixed, int n_wg, hipStream_t st
     return mixed ? q5k_launch_decode<BT, 1, true>(a, n_wg, st) : q5k_launch_decode<BT, 1, false>(a, n_wg, st);
 }
 
+// Fewest tokens of a Q5_K launch that take the prompt-step GEMM.  Above QMP_MIN_TOKENS (96) because the chunked path below splits K and the
+// prompt GEMM does not: the Llama-3-8B down projection (4096 x 14336: 16 row blocks, 56 k-blocks in a row) takes 184..186 us from 96 to 256
+// tokens on the GEMM against 35.5 us per 32-token chunk (107 us at 96, 142 us at 128 tokens) -- it wins from the sixth chunk on, gate|up
+// (67 against 132 us at 96 tokens) from the start.  DESIGN.md section 5b has the table.
+#define Q5P_MIN_TOKENS 192
 // every launch with a Q5_K segment (mi355_qmm_launch has validated K, B > 0 and the segment count)
 static int q5k_route(QmmArgs a, hipStream_t st) {
     bool pure = true, div2 = true;
@@ -450,6 +456,12 @@ static int q5k_route(QmmArgs a, hipStream_t st) {
     if (a.moe_expert || a.grp_n > 1 || a.blk_tab || g_qmm_exact) return (int)hipErrorNotSupported;
     if (a.paired && (a.nseg != 2 || a.seg[0].n_tiles != a.seg[1].n_tiles)) return (int)hipErrorInvalidValue;
     qmg_stream(st).chain.valid = false;                 // no activation image is staged for a successor
+    if (a.B >= Q5P_MIN_TOKENS && g_tune_prefill_gemm) {
+        // prompt step: the Q5_K arms of the prompt-step GEMM (qmm_prefill.inc), one GEMM per run of segments of one type;
+        // mi355_set_tuning(6, 0) = the 32-token chunks below (A/B)
+        const int rcq = qpg_launch(a, st);
+        if (rcq != (int)hipErrorNotSupported) return rcq;
+    }
     // tiles per workgroup: two amortise the activation staging where >= ~4 workgroups per CU remain; gate / up pairs are two by construction
     const int R = a.paired ? 2 : ((div2 && total_tiles / 2 >= 1024) ? 2 : 1);
     const int n_wg = a.paired ? a.seg[0].n_tiles : total_tiles / R;

@@ -38,7 +38,7 @@ extern "C" {
 #define MI355_KV_PAGED_FP8 2 /* the same with 1-byte OCP e4m3fn elements (x = 16): `--kvcache-dtype fp8` (host layers) */
 /* ggml tensor type ids (GGUF) */
 #define MI355_GGML_Q4_K 12
-#define MI355_GGML_Q5_K 13     /* 176-byte blocks; kernels of its own (csrc/qmm_q5k.inc) */
+#define MI355_GGML_Q5_K 13     /* 176-byte blocks; kernels of its own (csrc/qmm_q5k.inc) + arms of the prompt-step GEMM */
 #define MI355_GGML_Q6_K 14
 #define MI355_GGML_Q8_0 8      /* TP shards the reference re-quantises (quantized_var_builder.rs:234-269); native blocks, no repack */
 /* swap directions */
@@ -275,7 +275,9 @@ typedef struct mi355_qmm_desc {
 } mi355_qmm_desc;
 /* Types per segment: Q4_K, Q5_K, Q6_K in any mix (Q8_0: one segment, STORE / RESID).  A descriptor with a Q5_K segment runs on
  * kernels of its own and is refused with hipErrorNotSupported (801), nothing computed, when it carries moe_expert_ids,
- * group_count > 1 or group_block_table; it takes no chain hint (chain_next is ignored). */
+ * group_count > 1 or group_block_table; it takes no chain hint (chain_next is ignored).  From 192 tokens on it takes the
+ * prompt-step GEMM like the other types (one GEMM per run of segments of one type; mi355_set_tuning(6, 0) = 32-token chunks of the
+ * 9..32-token kernel, (24, 1) = hi + lo activation planes, (48, 0) = epilogue in a launch of its own). */
 int mi355_qmatmul_fused(const mi355_qmm_desc* desc, int64_t stream);
 /* MoE routing on the device (MlpOrMoe::forward, quantized_llama.rs:56-123, without the host round trip):
  * logits = gate_inp . rms_norm(x) ; softmax ; top-k (descending, ties -> lower expert id, as the stable sort there);
