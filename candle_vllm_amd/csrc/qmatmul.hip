@@ -26,6 +26,7 @@
 #include <string.h>
 #include <map>
 #include <mutex>
+#include <type_traits>
 #include <utility>
 
 #define Q4K_BLOCK 144
@@ -1493,252 +1494,6 @@ __global__ void __launch_bounds__(256) qmm_epilogue_grp_kernel(const QmmArgs a, 
 //  the chain longer, more workgroups hide it.  Deleted.)
 #include "qmm_wide1_gemm.inc"
 
-// Scratch of the wide / prompt paths (activation images, split-K partials, the prompt-step workspace) belongs to the
-// (device, stream) that launches: two models on two streams never share an image, growing a buffer never frees memory a
-// captured graph still replays from (scratch.cpp).  The chain hint is per (device, stream) too.
-// image staged by the last chained epilogue: valid for exactly the next wide launch if it consumes the same activations
-struct QmgChainState { bool valid; const void* x; int B, K, MT, buf; const float* norm_w; hipStream_t st; int sp; int x_dtype = MI355_DTYPE_F32;
-                       int grp = 1; int64_t grp_stride = 0;                       // grouped launch: groups and elements between their activations
-                       // the images were built WITHOUT their activations ever being written to `x` (mi355_internal_moe_stage_grouped: `x` is
-                       // only the key the consumer will present).  A launch that presents this key and cannot take the images must fail, it
-                       // must never stage from `x` (stale rows, silently wrong results -- ADVICE r5)
-                       bool prestaged = false; };
-struct QmgStream { int cur = 0; QmgChainState chain = {false, nullptr, 0, 0, 0, 0, nullptr, nullptr, 0}; };
-static std::mutex g_qmg_mu;
-static std::map<std::pair<int, hipStream_t>, QmgStream> g_qmg_streams;
-static QmgStream& qmg_stream(hipStream_t st) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    std::lock_guard<std::mutex> lock(g_qmg_mu);
-    return g_qmg_streams[std::make_pair(dev, st)];              // std::map: the reference stays valid across later inserts
-}
-// ONE statement of "a grouped mat-mul of B token rows runs as the z extent of the 9..32-token launches" (mi355_qmm_launch takes that path,
-// mi355_internal_moe_stage_grouped builds images only for it, mi355_internal_moe_scatter_combine_to_image stages only for it): three hand
-// copies of this condition had to agree for the fused MoE staging to be correct.  Defined below the tuning switches.
-static bool qmg_wide_one_launch(int B);
-static int g_tune_exact_act = 0;                              // mi355_set_tuning(24, 1): "exact" activations on the 9..32-token and prompt paths: f16 hi + lo planes (22 bits) instead of one f16 plane
-static int g_tune_chain = 1;                                  // mi355_set_tuning(9, 0): never chain (A/B experiments)
-// k-split of the 9..32-token launches: split K until a launch has QMG_KS_TARGET (row tile, k-split) slots = 4 consumer waves per CU,
-// keeping >= QMG_KS_MINKB k-blocks per workgroup.  (Measured at batch 32: targets 512 / 768 / 1024 / 1280 / 1536 / 2048 / 4096 ->
-// 4081 / 4634 / 4835-4900 / 4737 / 4742 / 4686 / 4607 tok/s: less splitting = fewer partial sums for the epilogue and longer pipelines.)
-#define QMG_KS_TARGET 1024
-#define QMG_KS_MINKB 2
-#define QMG_GRP_KS_TARGET 4096                                // the same for grouped launches (slots of all groups)
-static inline int qmg_buf(void** p, int key, size_t need, hipStream_t st) { return mi355_scratch_get(p, key, need, st, false); }
-
-template <int MT>
-static int qmg_launch(const QmmArgs& a0, hipStream_t st) {
-    QmmArgs a = a0;
-    if (a.paired) a.paired = 0;                 // slots are plain (segment, tile) order; the epilogue pairs gate/up rows
-    const int nkb = a.K / 256;
-    int n_slots = 0;
-    for (int s = 0; s < a.nseg; ++s) n_slots += a.seg[s].n_tiles;
-    const int ldp = n_slots * 16;
-    const size_t kbb = qmg_kb_bytes(MT);
-    int ks = 1;
-    while (n_slots * ks < QMG_KS_TARGET && nkb / (ks * 2) >= QMG_KS_MINKB) ks *= 2;
-    // activation image: staged by the previous launch's epilogue (chain) or by the prep kernel now
-    QmgStream& qs = qmg_stream(st);
-    const bool chained = qs.chain.valid && qs.chain.x == a.x && qs.chain.B == a.B && qs.chain.K == a.K &&
-                         qs.chain.MT == MT && qs.chain.sp == 0 && qs.chain.norm_w == a.norm_w && qs.chain.st == st &&
-                         a.x_dtype == MI355_DTYPE_F32 && a.ldx == a.K;
-    qs.chain.valid = false;
-    const int cur = chained ? qs.chain.buf : qs.cur;
-    int rc = 0;
-    void* imgp = nullptr;
-    // (a chained image was sized by the epilogue that staged it: the same request returns the same buffer)
-    rc = qmg_buf(&imgp, cur ? MI355_SCR_QMM_IMG1 : MI355_SCR_QMM_IMG0, kbb * nkb + (size_t)nkb * MT * 8 * sizeof(float), st);
-    if (rc) return rc;
-    void* partp = nullptr;
-    rc = qmg_buf(&partp, MI355_SCR_QMM_PART, (size_t)ks * MT * 8 * ldp * sizeof(float), st);
-    if (rc) return rc;
-    float* const part = static_cast<float*>(partp);
-    static Mi355DevOnce attr_done;
-    if (!attr_done.done()) {
-        (void)hipFuncSetAttribute((const void*)qmm_gemm_kernel<MT, MI355_GGML_Q4_K>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)qmm_gemm_kernel<MT, MI355_GGML_Q6_K>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)qmm_gemm2_kernel<MT, MI355_GGML_Q4_K, MI355_GGML_Q6_K>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr_done.set();
-    }
-    uint8_t* img = static_cast<uint8_t*>(imgp);
-    float* ssp = reinterpret_cast<float*>(img + kbb * nkb);                 // [nkb][MT*8] after the image
-    if (!chained) hipLaunchKernelGGL((qmm_prep2_kernel<MT>), dim3(nkb, MT), dim3(256), 0, st, img, ssp, a, kbb);
-    // one GEMM launch per run of same-type segments: the type-specialised builds need no schedule pinning and do not
-    // spill (the mixed build did); each run writes its own columns of the partial-sum buffer
-    int s_split = 0, slots0 = 0;                                     // exactly one Q4_K run followed by one Q6_K run: one launch
-    while (s_split < a.nseg && a.seg[s_split].type == MI355_GGML_Q4_K) slots0 += a.seg[s_split++].n_tiles;
-    bool two_runs = s_split > 0 && s_split < a.nseg;
-    for (int q = s_split; q < a.nseg; ++q) two_runs = two_runs && a.seg[q].type == MI355_GGML_Q6_K;
-    if (two_runs) {
-        const int slots1 = n_slots - slots0;
-        const dim3 ggrid((slots0 + QMG_NC - 1) / QMG_NC + (slots1 + QMG_NC - 1) / QMG_NC, ks);
-        hipLaunchKernelGGL((qmm_gemm2_kernel<MT, MI355_GGML_Q4_K, MI355_GGML_Q6_K>), ggrid, dim3(512), 2 * kbb, st, a, img, part, ldp, s_split, slots0, slots1);
-    }
-    for (int s0 = 0, slot_base = 0; s0 < a.nseg && !two_runs;) {
-        int s1 = s0 + 1;
-        while (s1 < a.nseg && a.seg[s1].type == a.seg[s0].type) ++s1;
-        QmmArgs r = a;
-        r.nseg = s1 - s0;
-        int run_slots = 0;
-        for (int q = 0; q < r.nseg; ++q) { r.seg[q] = a.seg[s0 + q]; run_slots += r.seg[q].n_tiles; }
-        const dim3 ggrid((run_slots + QMG_NC - 1) / QMG_NC, ks);
-        if (r.seg[0].type == MI355_GGML_Q4_K)
-            hipLaunchKernelGGL((qmm_gemm_kernel<MT, MI355_GGML_Q4_K>), ggrid, dim3(512), 2 * kbb, st, r, img, part, ldp, run_slots, slot_base);
-        else
-            hipLaunchKernelGGL((qmm_gemm_kernel<MT, MI355_GGML_Q6_K>), ggrid, dim3(512), 2 * kbb, st, r, img, part, ldp, run_slots, slot_base);
-        slot_base += run_slots;
-        s0 = s1;
-    }
-    // chain: this epilogue also stages the image of the next wide mat-mul (x = our out) into the other buffer
-    QmgChainOut ch{nullptr, nullptr, nullptr, 0, 0, 0, 0};
-    const bool want = g_tune_chain && a.chain_next && a.next_k > 0 && (a.next_k % 256) == 0 && a.ldo == a.next_k &&
-                      (a.epi == MI355_EPI_RESID || a.epi == MI355_EPI_SILU_MUL || a.epi == MI355_EPI_STORE) &&
-                      (a.epi == MI355_EPI_SILU_MUL ? a.seg[0].n_rows == a.next_k : (a.nseg == 1 && a.seg[0].n_rows == a.next_k));
-    if (want) {
-        const int other = cur ^ 1, nkb2 = a.next_k / 256;
-        void* onext = nullptr;
-        rc = qmg_buf(&onext, other ? MI355_SCR_QMM_IMG1 : MI355_SCR_QMM_IMG0, kbb * nkb2 + (size_t)nkb2 * MT * 8 * sizeof(float), st);
-        if (rc) return rc;
-        uint8_t* oimg = static_cast<uint8_t*>(onext);
-        ch = QmgChainOut{oimg, reinterpret_cast<float*>(oimg + kbb * nkb2), a.next_norm_w, a.next_k, MT, kbb, 0};
-        qs.chain = QmgChainState{true, a.out, a.B, a.next_k, MT, other, a.next_norm_w, st, 0};
-    }
-    qs.cur = cur;
-    hipLaunchKernelGGL(qmm_epilogue_kernel, dim3((ldp + 255) / 256, want ? MT * 8 : a.B), dim3(256), 0, st, a, part, ldp, ks,
-                       MT * 8, ssp, ch);
-    return (int)hipGetLastError();
-}
-
-// single-plane launcher (qmm_wide1.inc, qmm_wide1_gemm.inc): MT = m-tiles of 16 tokens (1: 9..16 tokens, 2: 17..32)
-template <int MT>
-static int qw1_launch(const QmmArgs& a0, hipStream_t st) {
-    QmmArgs a = a0;
-    if (a.paired) a.paired = 0;
-    const int nkb = a.K / 256;
-    int n_slots = 0;
-    for (int s = 0; s < a.nseg; ++s) n_slots += a.seg[s].n_tiles;
-    const int ldp = n_slots * 16, BP = MT * 16;
-    const size_t kbb = qw1_kb_bytes(MT);
-    // grouped launch: G mat-muls of these shapes in the z extent of every launch (the experts of a mixture-of-experts layer)
-    const int G = a.grp_n > 1 ? a.grp_n : 1;
-    int ks = 1;
-    if (G > 1) { while ((int64_t)n_slots * G * ks < QMG_GRP_KS_TARGET && nkb / (ks * 2) >= QMG_KS_MINKB) ks *= 2; }
-    else { while (n_slots * ks < QMG_KS_TARGET && nkb / (ks * 2) >= QMG_KS_MINKB) ks *= 2; }
-#ifndef QW1_Q6K_LONGK_WGS
-#define QW1_Q6K_LONGK_WGS 0
-#endif
-    if (QW1_Q6K_LONGK_WGS > 0 && G == 1 && a.nseg == 1 && nkb >= 32 && a.seg[0].type == MI355_GGML_Q6_K) {
-        // Rounds 4-5 (two MFMA chains per Q6_K weight, 411 VALU per tile and k-block: profiles/r03_pmc_sq_b32_set1.json): the long-K Q6_K
-        // launch (the down projection: 256 tiles x 56 k-blocks) was bound by its unpack arithmetic, and 37 x 14 = 518 workgroups -- two per
-        // CU, the second one's waves in the first's stalls -- beat the power-of-two split (37 x 4): 27.6 -> 23.8 us.  With ONE operand per
-        // weight (round 6, QW1_Q6K_ONE_PLANE) the arithmetic is no longer the bound and the 14 partial sums per output are pure cost:
-        // same box, ragged batch-32 step: 14 splits 6515 / 6529 tok/s, 7 splits 6699 / 6667, the general rule's 4 splits 6749 / 6729
-        // (profiles/r06_b32_q6k_ab.txt) -- the special case is off (-DQW1_Q6K_LONGK_WGS=512 builds it back for A/B).
-        const int n_wg = (n_slots + QMG_NC - 1) / QMG_NC;
-        const int cus = QW1_Q6K_LONGK_WGS;
-        if (n_wg * ks < cus) {
-            int want = (cus + n_wg - 1) / n_wg;
-            while (want > 1 && nkb / want < 4) --want;
-            if (want > ks) ks = want;
-        }
-    }
-    // (gate/up, 256 workgroups of 16 k-blocks: a split into 2 x 8 for two workgroups per CU measured +-0.1 % on the batch-32 step, round 4)
-    {   // no empty split: the kernels walk ceil(nkb / ks) k-blocks per split, and every split's partial sums are added up
-        const int kb_per = (nkb + ks - 1) / ks;
-        ks = (nkb + kb_per - 1) / kb_per;
-    }
-    QmgStream& qs = qmg_stream(st);
-    const bool chained = qs.chain.valid && qs.chain.x == a.x && qs.chain.B == a.B && qs.chain.K == a.K &&
-                         qs.chain.MT == MT && qs.chain.sp == 1 && qs.chain.norm_w == a.norm_w && qs.chain.st == st &&
-                         a.x_dtype == qs.chain.x_dtype && a.ldx == a.K && qs.chain.grp == G &&
-                         (G == 1 || qs.chain.grp_stride == a.grp_x);
-    const bool orphan = qs.chain.valid && qs.chain.prestaged && qs.chain.x == a.x && !chained;
-    qs.chain.valid = false;
-    if (orphan) {                                                       // the images behind this key were staged for another launch shape,
-        mi355_note_error((int)hipErrorInvalidValue);                     // and `x` itself was never written: refuse instead of staging stale rows
-        return (int)hipErrorInvalidValue;
-    }
-    const int cur = chained ? qs.chain.buf : qs.cur;
-    int rc = 0;
-    void* imgp = nullptr;
-    // (a group's image + sum-of-squares partials, rounded to the DMA granule: group e's lie e * imgb bytes after group 0's)
-    const size_t imgb = (kbb * nkb + (size_t)nkb * BP * sizeof(float) + 1023) / 1024 * 1024;
-    rc = qmg_buf(&imgp, cur ? MI355_SCR_QMM_IMG1 : MI355_SCR_QMM_IMG0, G > 1 ? G * imgb : kbb * nkb + (size_t)nkb * BP * sizeof(float), st);
-    if (rc) return rc;
-    void* partp = nullptr;
-    rc = qmg_buf(&partp, MI355_SCR_QMM_PART, (size_t)G * ks * BP * ldp * sizeof(float), st);
-    if (rc) return rc;
-    float* const part = static_cast<float*>(partp);
-    static Mi355DevOnce attr_done;
-    if (!attr_done.done()) {
-        (void)hipFuncSetAttribute((const void*)qw1_gemm_kernel<MT, MI355_GGML_Q4_K>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)qw1_gemm_kernel<MT, MI355_GGML_Q6_K>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)qw1_gemm2_kernel<MT, MI355_GGML_Q4_K, MI355_GGML_Q6_K>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)qw1_gemm_grp_kernel<MT, MI355_GGML_Q4_K>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)qw1_gemm_grp_kernel<MT, MI355_GGML_Q6_K>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)qw1_gemm2_grp_kernel<MT, MI355_GGML_Q4_K, MI355_GGML_Q6_K>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr_done.set();
-    }
-    uint8_t* img = static_cast<uint8_t*>(imgp);
-    float* ssp = reinterpret_cast<float*>(img + kbb * nkb);                 // [nkb][BP] after the image
-    // chain: the epilogue also stages the image of the next wide mat-mul (x = our out) into the other buffer
-    QmgChainOut ch{nullptr, nullptr, nullptr, 0, 0, 0, 0};
-    size_t imgb2 = 0;
-    const bool want = g_tune_chain && a.chain_next && a.next_k > 0 && (a.next_k % 256) == 0 && a.ldo == a.next_k &&
-                      (a.epi == MI355_EPI_RESID || a.epi == MI355_EPI_SILU_MUL || a.epi == MI355_EPI_STORE) &&
-                      (a.epi == MI355_EPI_SILU_MUL ? a.seg[0].n_rows == a.next_k : (a.nseg == 1 && a.seg[0].n_rows == a.next_k));
-    if (want) {
-        const int other = cur ^ 1, nkb2 = a.next_k / 256;
-        void* onext = nullptr;
-        imgb2 = (kbb * nkb2 + (size_t)nkb2 * BP * sizeof(float) + 1023) / 1024 * 1024;
-        rc = qmg_buf(&onext, other ? MI355_SCR_QMM_IMG1 : MI355_SCR_QMM_IMG0, G > 1 ? G * imgb2 : kbb * nkb2 + (size_t)nkb2 * BP * sizeof(float), st);
-        if (rc) return rc;
-        uint8_t* oimg = static_cast<uint8_t*>(onext);
-        ch = QmgChainOut{oimg, reinterpret_cast<float*>(oimg + kbb * nkb2), a.next_norm_w, a.next_k, MT, kbb, 1};
-    }
-    const QwGroup grp{a.grp_x, a.grp_out, (int64_t)imgb, (int64_t)ks * BP * ldp, (int64_t)imgb2};
-    const QwFuse fz{};                                                // unread kernel argument (qmm_wide1_gemm.inc)
-    if (!chained && G > 1) hipLaunchKernelGGL((qw1_prep_grp_kernel<MT>), dim3(nkb, MT * 2, G), dim3(256), 0, st, img, ssp, a, kbb, grp);
-    else if (!chained) hipLaunchKernelGGL((qw1_prep_kernel<MT>), dim3(nkb, MT * 2), dim3(256), 0, st, img, ssp, a, kbb);
-    int s_split = 0, slots0 = 0;                                     // exactly one Q4_K run followed by one Q6_K run: one launch
-    while (s_split < a.nseg && a.seg[s_split].type == MI355_GGML_Q4_K) slots0 += a.seg[s_split++].n_tiles;
-    bool two_runs = s_split > 0 && s_split < a.nseg;
-    for (int q = s_split; q < a.nseg; ++q) two_runs = two_runs && a.seg[q].type == MI355_GGML_Q6_K;
-    if (two_runs) {
-        const int slots1 = n_slots - slots0;
-        const dim3 ggrid((slots0 + QMG_NC - 1) / QMG_NC + (slots1 + QMG_NC - 1) / QMG_NC, ks, G);
-        if (G > 1) hipLaunchKernelGGL((qw1_gemm2_grp_kernel<MT, MI355_GGML_Q4_K, MI355_GGML_Q6_K>), ggrid, dim3(512), QW1_NB * kbb, st, a, img, part, ldp, s_split, slots0, slots1, fz, grp);
-        else hipLaunchKernelGGL((qw1_gemm2_kernel<MT, MI355_GGML_Q4_K, MI355_GGML_Q6_K>), ggrid, dim3(512), QW1_NB * kbb, st, a, img, part, ldp, s_split, slots0, slots1, fz);
-    }
-    for (int s0 = 0, slot_base = 0; s0 < a.nseg && !two_runs;) {
-        int s1 = s0 + 1;
-        while (s1 < a.nseg && a.seg[s1].type == a.seg[s0].type) ++s1;
-        QmmArgs r = a;
-        r.nseg = s1 - s0;
-        int run_slots = 0;
-        for (int q = 0; q < r.nseg; ++q) { r.seg[q] = a.seg[s0 + q]; r.moe_stride[q] = a.moe_stride[s0 + q]; run_slots += r.seg[q].n_tiles; }
-        const dim3 ggrid((run_slots + QMG_NC - 1) / QMG_NC, ks, G);
-        if (G > 1) {
-            if (r.seg[0].type == MI355_GGML_Q4_K)
-                hipLaunchKernelGGL((qw1_gemm_grp_kernel<MT, MI355_GGML_Q4_K>), ggrid, dim3(512), QW1_NB * kbb, st, r, img, part, ldp, run_slots, slot_base, fz, grp);
-            else
-                hipLaunchKernelGGL((qw1_gemm_grp_kernel<MT, MI355_GGML_Q6_K>), ggrid, dim3(512), QW1_NB * kbb, st, r, img, part, ldp, run_slots, slot_base, fz, grp);
-        } else if (r.seg[0].type == MI355_GGML_Q4_K)
-            hipLaunchKernelGGL((qw1_gemm_kernel<MT, MI355_GGML_Q4_K>), ggrid, dim3(512), QW1_NB * kbb, st, r, img, part, ldp, run_slots, slot_base, fz);
-        else
-            hipLaunchKernelGGL((qw1_gemm_kernel<MT, MI355_GGML_Q6_K>), ggrid, dim3(512), QW1_NB * kbb, st, r, img, part, ldp, run_slots, slot_base, fz);
-        slot_base += run_slots;
-        s0 = s1;
-    }
-    if (want) { qs.chain = QmgChainState{true, a.out, a.B, a.next_k, MT, cur ^ 1, a.next_norm_w, st, 1}; qs.chain.grp = G; qs.chain.grp_stride = a.grp_out; }
-    qs.cur = cur;
-    if (G > 1)
-        hipLaunchKernelGGL(qmm_epilogue_grp_kernel, dim3((ldp + 255) / 256, want ? BP : a.B, G), dim3(256), 0, st, a, part, ldp, ks, BP, ssp, ch, grp);
-    else
-        hipLaunchKernelGGL(qmm_epilogue_kernel, dim3((ldp + 255) / 256, want ? BP : a.B), dim3(256), 0, st, a, part, ldp, ks, BP, ssp, ch);
-    return (int)hipGetLastError();
-}
-
 // ---- the merge of the balanced attention stream's partials, fused with the staging of the NEXT mat-mul's activation image (round 4).
 // At batch 9..32 the attention output feeds wo through the 9..32-token path, whose image (one f16 plane, block scale per token and
 // k-block) was built by a launch of its own (qw1_prep_kernel, 4.9 us per layer) right after the merge launch (4.7 us): a k-block = 256
@@ -1801,354 +1556,11 @@ __global__ void __launch_bounds__(256) pa_stream_reduce_img_kernel(uint16_t* __r
         qw1_prep_entry(img, ssp, e8, b < B, nullptr, MT, kbb, kb, b, (int)threadIdx.x);
     }
 }
-/* host layers: merge the stream's partials (mi355_internal_paged_attention_v2_partials) into `out` bf16 [B, H, 128] AND stage the image of
- * the wide mat-mul that reads `out` next on this stream (x = out, k = H * 128, no norm).  9 <= B <= 32, H even.  -4: not this shape. */
-extern "C" int mi355_internal_pa_stream_reduce_to_image(void* out, const float* tmp_out, const float* max_logits, const float* exp_sums,
-                                                        const uint32_t* context_lens, int32_t B, int32_t H, int32_t W, int32_t slots,
-                                                        int64_t stream) {
-    if (B < 9 || B > 32 || (H & 1) || W < 1 || W > 64 || g_tune_exact_act || !g_tune_chain) return -4;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const int MT = B <= 16 ? 1 : 2, BP = MT * 16, K = H * 128, nkb = K / 256;
-    const size_t kbb = qw1_kb_bytes(MT);
-    QmgStream& qs = qmg_stream(st);
-    const int other = qs.cur ^ 1;
-    void* p = nullptr;
-    const int rc = qmg_buf(&p, other ? MI355_SCR_QMM_IMG1 : MI355_SCR_QMM_IMG0, kbb * nkb + (size_t)nkb * BP * sizeof(float), st);
-    if (rc) return rc;
-    uint8_t* img = static_cast<uint8_t*>(p);
-    float* ssp = reinterpret_cast<float*>(img + kbb * nkb);
-    const dim3 grid(H / 2, BP);
-    if (MT == 1)
-        hipLaunchKernelGGL((pa_stream_reduce_img_kernel<1>), grid, dim3(256), 0, st, static_cast<uint16_t*>(out), tmp_out, max_logits, exp_sums,
-                           context_lens, B, H, W, slots, img, ssp, kbb);
-    else
-        hipLaunchKernelGGL((pa_stream_reduce_img_kernel<2>), grid, dim3(256), 0, st, static_cast<uint16_t*>(out), tmp_out, max_logits, exp_sums,
-                           context_lens, B, H, W, slots, img, ssp, kbb);
-    QmgChainState cs{true, out, B, K, MT, other, nullptr, st, 1};
-    cs.x_dtype = MI355_DTYPE_BF16;
-    qs.chain = cs;
-    return (int)hipGetLastError();
-}
 
 // ================================================================================================
-// Prompt-step path (num_tokens >= QMP_MIN_TOKENS): the matmul is compute-bound, so it is run as a GEMM on the matrix cores
-// (qmm_prefill.inc) instead of streaming the quantised weights once per 32 tokens.
-#define QMP_MIN_TOKENS 96                                  // fewest tokens that take the prompt-step GEMM
-
-static int g_tune_qpg_fepi = 1;                            // mi355_set_tuning(48, 0): A/B, separate epilogue launch.  Default: the prompt-step GEMM applies the epilogue itself (Q4_K launches; store / residual / SiLU * up; round 4: +7 % on the prompt step)
-
+// Prompt-step GEMM kernels (launcher: qpg_launch)
 #include "qmm_prefill.inc"
 
-// hand-written prompt-step GEMM (qmm_prefill.inc); returns hipErrorNotSupported for launches it does not cover (then the
-// caller streams the weights 32 tokens at a time)
-static int qpg_launch(const QmmArgs& a0, hipStream_t st) {
-    QmmArgs a = a0;
-    a.paired = 0;
-    for (int s = 0; s < a.nseg; ++s)
-        if (!is_kquant(a.seg[s].type) || (a.seg[s].type == MI355_GGML_Q5_K && a.blk_tab)) return (int)hipErrorNotSupported;
-    if (a.moe_expert || (a.K & 255)) return (int)hipErrorNotSupported;
-    int n_slots = 0;
-    for (int s = 0; s < a.nseg; ++s) n_slots += a.seg[s].n_tiles;
-    const int T = a.B, K = a.K, ldp = n_slots * 16, nkb = K >> 8;
-    const int Tpad = (T + QPG_BM - 1) / QPG_BM * QPG_BM;
-    const int parts = g_tune_exact_act ? 2 : 1;             // activation planes of the f16 image (mi355_set_tuning(24, 1) = hi + lo)
-    // (a block-table launch only exists with the epilogue in the store loop: no C buffer -- it would be 1.9 GB for a Mixtral chunk)
-    const size_t xa_b = (size_t)K * Tpad * 2 * parts, sf_b = (size_t)nkb * Tpad * 32, rs_b = (size_t)Tpad * 4, c_b = a.blk_tab ? 0 : (size_t)T * ldp * 4;
-    void* ws = nullptr;
-    int rc = qmg_buf(&ws, MI355_SCR_QMP_WS, xa_b + sf_b + 2 * rs_b + c_b + 4096, st);
-    if (rc) return rc;
-    uint8_t* base = static_cast<uint8_t*>(ws);
-    QpgImg im;
-    im.xa = base; im.sfrag = base + xa_b;
-    im.row_scale = reinterpret_cast<float*>(base + xa_b + sf_b);
-    im.row_inv = im.row_scale + Tpad;
-    im.Tpad = Tpad;
-    im.parts = parts;
-    float* C = reinterpret_cast<float*>(base + xa_b + sf_b + 2 * rs_b);
-    static Mi355DevOnce attr_done;
-    if (!attr_done.done()) {
-        (void)hipFuncSetAttribute((const void*)qpg_gemm_kernel<MI355_GGML_Q4_K, 4, 2, 1, 8, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
-        (void)hipFuncSetAttribute((const void*)qpg_gemm_lds2_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-        (void)hipFuncSetAttribute((const void*)qpg_gemm_lds2_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-        (void)hipFuncSetAttribute((const void*)qpg_gemm_lds2_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-        (void)hipFuncSetAttribute((const void*)qpg_gemm_kernel<MI355_GGML_Q5_K, 4, 2, 1, 8, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
-        (void)hipFuncSetAttribute((const void*)qpg_gemm_lds2_kernel<true, false, MI355_GGML_Q5_K>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-        (void)hipFuncSetAttribute((const void*)qpg_gemm_lds2_kernel<false, false, MI355_GGML_Q5_K>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-        (void)hipFuncSetAttribute((const void*)qpg_gemm_q6k_kernel<2, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
-        (void)hipFuncSetAttribute((const void*)qpg_gemm_q6k_lds_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)qpg_gemm_q6k_lds_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)qpg_gemm_q6k_lds_kernel<true, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)qpg_gemm_q6k_lds_kernel<true, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr_done.set();
-    }
-    hipLaunchKernelGGL(qpg_rowprep_kernel, dim3(Tpad), dim3(256), 0, st, a, im);          // row statistics + image, one launch (workgroup = token)
-    // mi355_set_tuning(48, 1), the default: all segments Q4_K (or all Q5_K), one activation plane, and an epilogue that is a store /
-    // residual add / SiLU * up over two equal segments -> the GEMM writes the outputs itself, no C buffer, no epilogue launch
-    {
-        bool all_q4 = true, all_q5 = true;
-        for (int s = 0; s < a.nseg; ++s) { all_q4 = all_q4 && a.seg[s].type == MI355_GGML_Q4_K; all_q5 = all_q5 && a.seg[s].type == MI355_GGML_Q5_K; }
-        const bool epi_ok = a.epi == MI355_EPI_STORE || a.epi == MI355_EPI_RESID ||
-                            (a.epi == MI355_EPI_SILU_MUL && a.nseg == 2 && a.seg[0].n_tiles == a.seg[1].n_tiles && a.seg[0].n_rows == a.seg[1].n_rows);
-        if (g_tune_qpg_fepi && (all_q4 || all_q5) && epi_ok && parts == 1) {
-            QmmArgs r = a;
-            r.norm_w = nullptr;                                 // applied while the image was built
-            // 64 tokens x 256 rows per workgroup (waves 64 x 32), two workgroups per CU
-            const dim3 g_(Tpad / 64, (n_slots + 15) / 16), b_(512);
-            if (all_q5) hipLaunchKernelGGL((qpg_gemm_lds2_kernel<true, false, MI355_GGML_Q5_K>), g_, b_, (size_t)QPG5_BYTES, st, r, im, C, ldp, n_slots, 0);
-            else if (a.blk_tab) hipLaunchKernelGGL((qpg_gemm_lds2_kernel<true, true>), g_, b_, (size_t)QPG2_BYTES, st, r, im, C, ldp, n_slots, 0);
-            else hipLaunchKernelGGL((qpg_gemm_lds2_kernel<true>), g_, b_, (size_t)QPG2_BYTES, st, r, im, C, ldp, n_slots, 0);
-            return (int)hipGetLastError();
-        }
-        if (a.blk_tab) {
-            // block-table launches: Q4_K above; one Q6_K matrix with a store / residual epilogue here (the down projections of a Q4_K_M file)
-            if (a.nseg == 1 && a.seg[0].type == MI355_GGML_Q6_K && (a.epi == MI355_EPI_STORE || a.epi == MI355_EPI_RESID) && parts == 1 &&
-                g_tune_qpg_fepi) {
-                QmmArgs r = a;
-                r.norm_w = nullptr;
-                hipLaunchKernelGGL((qpg_gemm_q6k_lds_kernel<true, 2, true>), dim3(Tpad / 64, (n_slots + 15) / 16), dim3(512), (size_t)QPG6_LDS_BYTES, st, r, im, C,
-                                   ldp, n_slots, 0);
-                return (int)hipGetLastError();
-            }
-            return (int)hipErrorNotSupported;
-        }
-    }
-    // q | k | v of a prompt step (EPI_QKV_ROPE_CACHE, round 6): q and k (both Q4_K or both Q5_K) -- and v where it has their type -- go through the fused store loop
-    // (RoPE + bf16 + cache scatter in the GEMM); a Q6_K v (half the layers of a Q4_K_M file) keeps its own GEMM + the epilogue launch, which
-    // then sees q and k as empty segments (n_rows = 0: their columns of C were never written)
-#ifndef QPG_FUSE_Q6K
-#define QPG_FUSE_Q6K 1          // A/B builds: 0 = Q6_K prompt GEMMs write the C buffer and an epilogue launch follows (rounds 2-5)
-#endif
-#ifndef QPG6_SPLIT_SMALL
-#define QPG6_SPLIT_SMALL 1      // A/B builds: 0 = the Q6_K value projection always in 256-row workgroups
-#endif
-#ifndef QPG_FUSE_QKV
-#define QPG_FUSE_QKV 1          // A/B builds: 0 = q | k | v through the C buffer and the epilogue launch (rounds 2-5)
-#endif
-    // (from 1024 tokens: measured +0.7 % at 2048 and +1.2 % at 4096 tokens, -1.9 % at 512 -- profiles/r06_prompt_qkv_fused_ab.txt)
-    if (QPG_FUSE_QKV && T >= 1024 && g_tune_qpg_fepi && parts == 1 && a.epi == MI355_EPI_QKV_ROPE_CACHE && a.nseg == 3 &&
-        a.seg[0].type != MI355_GGML_Q6_K && a.seg[1].type == a.seg[0].type &&
-        (a.seg[2].type == a.seg[0].type || (QPG_FUSE_Q6K && a.seg[2].type == MI355_GGML_Q6_K))) {
-        const bool v4 = a.seg[2].type == a.seg[0].type;                 // v goes with q and k
-        const bool q5 = a.seg[0].type == MI355_GGML_Q5_K;
-        QmmArgs r = a;
-        r.norm_w = nullptr;                                         // applied while the image was built
-        if (!v4) r.nseg = 2;
-        int f_slots = 0;
-        for (int q = 0; q < r.nseg; ++q) f_slots += r.seg[q].n_tiles;
-        const dim3 gf(Tpad / 64, (f_slots + 15) / 16);
-        if (q5) hipLaunchKernelGGL((qpg_gemm_lds2_kernel<true, false, MI355_GGML_Q5_K>), gf, dim3(512), (size_t)QPG5_BYTES, st, r, im, C, ldp, f_slots, 0);
-        else hipLaunchKernelGGL((qpg_gemm_lds2_kernel<true>), gf, dim3(512), (size_t)QPG2_BYTES, st, r, im, C, ldp, f_slots, 0);
-        if (v4) return (int)hipGetLastError();
-        // v (Q6_K): its own GEMM with the fused store loop; q and k stay in the descriptor as EMPTY segments (no tiles) so that the value
-        // segment keeps its role (2 = v: bf16 + cache scatter, no rotation) and its row offsets
-        QmmArgs rv = a;
-        rv.norm_w = nullptr;
-        rv.seg[0].n_tiles = 0; rv.seg[1].n_tiles = 0;
-        // (one row tile per wave where two would leave CUs empty: 1024 rows x 2048 tokens = 128 workgroups of 256 rows)
-        const int vt = a.seg[2].n_tiles;
-        if (QPG6_SPLIT_SMALL && (Tpad / 64) * ((vt + 15) / 16) < mi355_num_cus())
-            hipLaunchKernelGGL((qpg_gemm_q6k_lds_kernel<true, 1>), dim3(Tpad / 64, (vt + 7) / 8), dim3(512), (size_t)QPG6_LDS_BYTES, st, rv, im, C, ldp, vt, 0);
-        else
-            hipLaunchKernelGGL((qpg_gemm_q6k_lds_kernel<true>), dim3(Tpad / 64, (vt + 15) / 16), dim3(512), (size_t)QPG6_LDS_BYTES, st, rv, im, C, ldp, vt, 0);
-        return (int)hipGetLastError();
-    }
-    for (int s0 = 0, slot_base = 0; s0 < a.nseg;) {
-        int s1 = s0 + 1;
-        while (s1 < a.nseg && a.seg[s1].type == a.seg[s0].type) ++s1;
-        QmmArgs r = a;
-        r.nseg = s1 - s0;
-        int run_slots = 0;
-        for (int q = 0; q < r.nseg; ++q) { r.seg[q] = a.seg[s0 + q]; run_slots += r.seg[q].n_tiles; }
-        if (r.seg[0].type == MI355_GGML_Q4_K) {
-            // 64 x 256, waves 64 x 32, two workgroups per CU
-            const dim3 g4(Tpad / 64, (run_slots + 15) / 16), b_(512);
-            if (parts == 1)                                             // one activation plane: image and weights through LDS by DMA
-                hipLaunchKernelGGL((qpg_gemm_lds2_kernel<false>), g4, b_, (size_t)QPG2_BYTES, st, r, im, C, ldp, run_slots, slot_base);
-            else                                                        // hi + lo planes ("exact" activations): the register-fed form
-                hipLaunchKernelGGL((qpg_gemm_kernel<MI355_GGML_Q4_K, 4, 2, 1, 8, 2>), g4, b_, (size_t)2 * 2 * 64 * QPG_ROWB, st, r, im, C, ldp, run_slots, slot_base);
-        } else if (r.seg[0].type == MI355_GGML_Q5_K) {                  // the same two kernels over Q5_K tiles
-            const dim3 g5(Tpad / 64, (run_slots + 15) / 16), b_(512);
-            if (parts == 1)
-                hipLaunchKernelGGL((qpg_gemm_lds2_kernel<false, false, MI355_GGML_Q5_K>), g5, b_, (size_t)QPG5_BYTES, st, r, im, C, ldp, run_slots, slot_base);
-            else
-                hipLaunchKernelGGL((qpg_gemm_kernel<MI355_GGML_Q5_K, 4, 2, 1, 8, 2>), g5, b_, (size_t)2 * 2 * 64 * QPG_ROWB, st, r, im, C, ldp, run_slots, slot_base);
-        } else {
-            if (parts == 1) {                      // Q6_K: 64 tokens x 256 rows per workgroup; token blocks fastest
-                const dim3 grid(Tpad / 64, (run_slots + 15) / 16);
-                // the whole mat-mul is this one Q6_K run and its epilogue is a store / residual add: fused store loop, no C buffer, no launch
-                // (from 4096 tokens -- measured: +1.2 % at 4096, -0.2 % at 2048: profiles/r06_prompt_q6k_fused_ab.txt)
-                if (QPG_FUSE_Q6K && g_tune_qpg_fepi && T >= 4096 && s0 == 0 && s1 == a.nseg && (a.epi == MI355_EPI_STORE || a.epi == MI355_EPI_RESID)) {
-                    r.norm_w = nullptr;
-                    hipLaunchKernelGGL((qpg_gemm_q6k_lds_kernel<true>), grid, dim3(512), (size_t)QPG6_LDS_BYTES, st, r, im, C, ldp, run_slots, 0);
-                    return (int)hipGetLastError();
-                }
-                hipLaunchKernelGGL((qpg_gemm_q6k_lds_kernel<false>), grid, dim3(512), (size_t)QPG6_LDS_BYTES, st, r, im, C, ldp, run_slots, slot_base);
-            } else {
-                const dim3 grid(Tpad / 32, (run_slots + 15) / 16);     // 32 tokens x 256 rows, register-fed: hi + lo planes ("exact" activations)
-                hipLaunchKernelGGL((qpg_gemm_q6k_kernel<2, 2>), grid, dim3(512), 16 * 1024, st, r, im, C, ldp, run_slots, slot_base);
-            }
-        }
-        slot_base += run_slots;
-        s0 = s1;
-    }
-    a.norm_w = nullptr;                                     // applied while the image was built
-    hipLaunchKernelGGL(qmm_epilogue_kernel, dim3((ldp + 255) / 256, T), dim3(256), 0, st, a, C, ldp, 1, T, (const float*)nullptr,
-                       QmgChainOut{nullptr, nullptr, nullptr, 0, 0, 0, 0}, (const float*)im.row_scale);
-    return (int)hipGetLastError();
-}
-
-
-// ------------------------------------------------------------------------------------------------ launcher
-void mi355_pa_set_fused(int v);
-void mi355_pa_set_wpb(int v);
-void mi355_pa_set_loop(int v);
-void mi355_dense_set_small(int key, int v);
-extern "C" void mi355_host_set_partition_override(int v);
-extern "C" void mi355_host_set_moe_group(int v);
-void mi355_prefill_set_fp8_generic(int v);
-void mi355_prefill_set_lds(int v);
-static int g_tune_prefill_gemm = 1;                        // mi355_set_tuning(6, v): 1 = prompt steps take the prompt-step GEMM, 0 = always stream the quantised weights (A/B)
-// ---- A/B switches.  The library honours exactly ten keys (documented in include/mi355_vllm.h; their defaults live in the table
-// below, which is applied through the same setters at load time, so `mi355_get_tuning` always returns the live value of a key);
-// every other key is ignored.
-static int32_t g_tune_shadow[64];
-static bool g_tune_shadow_set[64];
-static const int32_t kProductTuning[][2] = {{3, 1}, {5, 0}, {6, 1}, {9, 1}, {24, 0}, {30, 0}, {41, 1}, {44, 1}, {47, 1}, {48, 1}};
-static bool tuning_is_product_key(int32_t key) {
-    for (const auto& kv : kProductTuning) if (kv[0] == key) return true;
-    return false;
-}
-static void tuning_apply(int32_t key, int32_t value) {
-    if (key == 3) { mi355_pa_set_fused(value & 15); mi355_pa_set_wpb(value >> 4); }   // merge form | 16 x partitions per workgroup (0 = auto)
-    else if (key == 5) mi355_host_set_partition_override(value);
-    else if (key == 6) g_tune_prefill_gemm = value;
-    else if (key == 9) g_tune_chain = value;
-    else if (key == 24) g_tune_exact_act = value;
-    else if (key == 30) mi355_dense_set_small(30, value);           // bit mask of folded launches switched OFF (dense_gemv.hip)
-    else if (key == 41) mi355_host_set_moe_group(value);
-    else if (key == 44) mi355_pa_set_loop(value);
-    else if (key == 47) { mi355_prefill_set_lds(value & 1); mi355_prefill_set_fp8_generic((value >> 1) & 1); }
-    else if (key == 48) g_tune_qpg_fepi = value;
-}
-namespace {
-struct TuningInit {
-    TuningInit() {
-        for (const auto& kv : kProductTuning) { tuning_apply(kv[0], kv[1]); g_tune_shadow[kv[0]] = kv[1]; g_tune_shadow_set[kv[0]] = true; }
-    }
-} g_tuning_init;
-}
-/* 1 when the library honours `key` (the ten product keys) */
-extern "C" int32_t mi355_tuning_supported(int32_t key) {
-    if (key < 0 || key >= 64) return 0;
-    return tuning_is_product_key(key) ? 1 : 0;
-}
-extern "C" int32_t mi355_get_tuning(int32_t key) {
-    if (key < 0 || key >= 64 || !g_tune_shadow_set[key]) return INT32_MIN;
-    return g_tune_shadow[key];
-}
-extern "C" void mi355_set_tuning(int32_t key, int32_t value) {
-    if (!mi355_tuning_supported(key)) return;                       // any other key is ignored (and stays "never set")
-    g_tune_shadow[key] = value; g_tune_shadow_set[key] = true;
-    tuning_apply(key, value);
-}
-
-static size_t qmm_lds_bytes(int BT, int R, int NW) {
-    const size_t xw = (size_t)32 * 2 * BT * 16;
-    return (size_t)NW * xw + (size_t)NW * R * BT * 16 * 4 + (size_t)NW * BT * 4 + 64;
-}
-
-static int g_num_cus = 0;
-
-// Waves per workgroup: the largest NW in {8,4,2,1} for which every workgroup of the launch is resident at
-// once (no second dispatch round => no tail), judged by the occupancy the runtime reports for this variant.
-template <int BT, int R, int WT>
-static int qmm_pick_nw(int n_wg, int nkb) {
-    static int blocks_per_cu[4] = {-1, -1, -1, -1};       // NW = 8,4,2,1
-    g_num_cus = mi355_num_cus();                         // per device (common.h)
-    int pick = 1;
-    for (int i = 0; i < 3; ++i) {                         // never below 2 waves: one wave per tile serialises K
-        const int nw = 8 >> i;
-        if (nw > nkb) continue;
-        if (blocks_per_cu[i] < 0) {
-            int nb = 0;
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)qmm_kernel<BT, R, WT, 0, 1>, 64 * nw,
-                                                             qmm_lds_bytes(BT, R, nw)) != hipSuccess || nb < 1) nb = 1;
-            blocks_per_cu[i] = nb;
-        }
-        pick = nw;
-        if ((long)n_wg <= (long)blocks_per_cu[i] * g_num_cus) return nw;
-    }
-    // more workgroups than the chip holds even at 2 waves each: several rounds anyway -> 4 waves
-    return nkb >= 4 ? 4 : pick;
-}
-
-template <int BT, int R, int WT>
-static int qmm_launch_btrw(QmmArgs& a, int n_wg, hipStream_t st) {
-    a.kch = 0;
-    static Mi355DevOnce attr_done;
-    if (!attr_done.done()) {
-        (void)hipFuncSetAttribute((const void*)qmm_kernel<BT, R, WT, 0, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)qmm_kernel<BT, R, WT, 0, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)qmm_kernel<BT, R, WT, 1, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)qmm_kernel<BT, R, WT, 1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr_done.set();
-    }
-    // (token, slot) pairs of a mixture-of-experts launch are workgroups too: all of them should be resident at once
-    // the paired (gate / up) single-token launch runs TWO waves per workgroup: measured on the product build, alternated on one box
-    // (profiles/r06_b1_gateup_waves_ab.txt): 2 waves 1.841 ms per step, 4 waves 1.862, 8 waves 1.875.  The occupancy rule below picked 2 while
-    // the kernel needed 134 VGPRs and flipped to 4 when a register-allocation change brought it to 127 -- a choice that depends on the
-    // allocator's mood is not a choice (QMM_NW_PAIRED: A/B builds)
-#ifndef QMM_NW_PAIRED
-#define QMM_NW_PAIRED 2
-#endif
-    const int NW = (QMM_NW_PAIRED > 0 && a.paired && BT == 1 && !a.moe_expert && a.K / 256 >= QMM_NW_PAIRED)
-                       ? QMM_NW_PAIRED : qmm_pick_nw<BT, R, WT>(n_wg * (a.moe_expert ? a.moe_pairs : 1), a.K / 256);
-    const size_t shm = qmm_lds_bytes(BT, R, NW);
-    if (shm > 160 * 1024) return (int)hipErrorInvalidValue;
-    if (a.moe_expert) {
-        if constexpr (BT == 1) {
-            static Mi355DevOnce moe_attr_done;
-            if (!moe_attr_done.done()) {
-                (void)hipFuncSetAttribute((const void*)qmm_moe_kernel<R, WT, 0, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-                (void)hipFuncSetAttribute((const void*)qmm_moe_kernel<R, WT, 0, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-                (void)hipFuncSetAttribute((const void*)qmm_moe_kernel<R, WT, 1, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-                (void)hipFuncSetAttribute((const void*)qmm_moe_kernel<R, WT, 1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-                moe_attr_done.set();
-            }
-            const bool xb = a.x_dtype == MI355_DTYPE_BF16, nrm = a.norm_w != nullptr;
-            const dim3 mgrid(n_wg, a.moe_pairs), mblock(64 * NW);
-            if (xb && nrm) hipLaunchKernelGGL((qmm_moe_kernel<R, WT, 1, 1>), mgrid, mblock, shm, st, a);
-            else if (xb) hipLaunchKernelGGL((qmm_moe_kernel<R, WT, 1, 0>), mgrid, mblock, shm, st, a);
-            else if (nrm) hipLaunchKernelGGL((qmm_moe_kernel<R, WT, 0, 1>), mgrid, mblock, shm, st, a);
-            else hipLaunchKernelGGL((qmm_moe_kernel<R, WT, 0, 0>), mgrid, mblock, shm, st, a);
-        } else {
-            return (int)hipErrorInvalidValue;
-        }
-    } else {
-        const bool xb = a.x_dtype == MI355_DTYPE_BF16, nrm = a.norm_w != nullptr;
-        if (xb && nrm) hipLaunchKernelGGL((qmm_kernel<BT, R, WT, 1, 1>), dim3(n_wg), dim3(64 * NW), shm, st, a);
-        else if (xb) hipLaunchKernelGGL((qmm_kernel<BT, R, WT, 1, 0>), dim3(n_wg), dim3(64 * NW), shm, st, a);
-        else if (nrm) hipLaunchKernelGGL((qmm_kernel<BT, R, WT, 0, 1>), dim3(n_wg), dim3(64 * NW), shm, st, a);
-        else hipLaunchKernelGGL((qmm_kernel<BT, R, WT, 0, 0>), dim3(n_wg), dim3(64 * NW), shm, st, a);
-    }
-    return (int)hipGetLastError();
-}
-
-template <int BT, int R>
-static int qmm_launch_btr(QmmArgs& a, int wt, int n_wg, hipStream_t st) {
-    if (wt == MI355_GGML_Q4_K) return qmm_launch_btrw<BT, R, MI355_GGML_Q4_K>(a, n_wg, st);
-    if (wt == MI355_GGML_Q6_K) return qmm_launch_btrw<BT, R, MI355_GGML_Q6_K>(a, n_wg, st);
-    return qmm_launch_btrw<BT, R, 0>(a, n_wg, st);
-}
-
-template <int BT>
-static int qmm_launch_bt(QmmArgs& a, int R, int wt, int n_wg, hipStream_t st) {
-    if (R == 4) return qmm_launch_btr<BT, 4>(a, wt, n_wg, st);
-    if (R == 2) return qmm_launch_btr<BT, 2>(a, wt, n_wg, st);
-    return qmm_launch_btr<BT, 1>(a, wt, n_wg, st);
-}
-
-// Run one fused quantised mat-mul over batch rows [0,B) in M-tiles of 8 batch entries.
 // ================================================================================================
 // Q8_0 arm: tensor-parallel shards the reference re-quantises (dim-1 shards that cut a 256-wide k-quant block are
 // dequantised, narrowed and re-quantised to Q8_0 -- layers/quantized_var_builder.rs:234-269).  Native blocks
@@ -2198,208 +1610,8 @@ __global__ void __launch_bounds__(64) q8_0_matmul_kernel(const QmmArgs a) {
         }
     }
 }
-static int q8_0_launch(const QmmArgs& a, hipStream_t st) {
-    if (a.nseg != 1 || a.norm_w || a.moe_expert || (a.epi != MI355_EPI_STORE && a.epi != MI355_EPI_RESID) || (a.K % 32) || a.K <= 0)
-        return (int)hipErrorInvalidValue;
-    if (a.B == 0) return 0;
-    hipLaunchKernelGGL(q8_0_matmul_kernel, dim3(a.seg[0].n_rows, (a.B + 7) / 8), dim3(64), 0, st, a);
-    return (int)hipGetLastError();
-}
 
-// ---- parity mode 2 (tests only; kernel in qmm_exact.inc): switch + launcher
-static int g_qmm_exact = 0;
-#include "qmm_q5k.inc"     // Q5_K: its own decode and 9..32-token kernels + launcher (q5k_route)
-extern "C" void mi355_internal_qmm_set_exact(int32_t on) {
-    g_qmm_exact = on ? 1 : 0;
-    // an exact launch stages no activation image for its successor: forget every chain hint, in both directions of the switch
-    std::lock_guard<std::mutex> lk(g_qmg_mu);
-    for (auto& kv : g_qmg_streams) kv.second.chain.valid = false;
-}
-extern "C" int32_t mi355_internal_qmm_get_exact(void) { return g_qmm_exact; }
-
-// one launch per token
-static int qmm_exact_launch(QmmArgs a, hipStream_t st) {
-    const int B = a.B;
-    const size_t xes = (a.x_dtype == MI355_DTYPE_BF16) ? 2 : 4;
-    const uint8_t* x0 = static_cast<const uint8_t*>(a.x);
-    float* out0 = a.out;
-    const float* resid0 = a.resid;
-    uint16_t* q0 = a.q_out;
-    const int64_t* pos0 = a.positions;
-    const int64_t* slot0 = a.slot_mapping;
-    int total_tiles = 0;
-    for (int s = 0; s < a.nseg; ++s) total_tiles += a.seg[s].n_tiles;
-    for (int b = 0; b < B; ++b) {
-        a.B = 1;
-        a.x = x0 + (size_t)b * a.ldx * xes;
-        a.out = out0 ? out0 + (size_t)b * a.ldo : nullptr;
-        a.resid = resid0 ? resid0 + (size_t)b * a.ldo : nullptr;
-        a.q_out = q0 ? q0 + (size_t)b * a.Hq * a.D : nullptr;
-        a.positions = pos0 ? pos0 + b : nullptr;
-        a.slot_mapping = slot0 ? slot0 + b : nullptr;
-        if (a.paired) hipLaunchKernelGGL((qmm_exact_kernel<2>), dim3(a.seg[0].n_tiles), dim3(256), 0, st, a);
-        else hipLaunchKernelGGL((qmm_exact_kernel<1>), dim3(total_tiles), dim3(256), 0, st, a);
-    }
-    return (int)hipGetLastError();
-}
-
-static bool qmg_wide_one_launch(int B) {
-    return B > 8 && B <= 8 * QMW_MAXMT && !g_tune_exact_act && !g_qmm_exact && !(B >= QMP_MIN_TOKENS && g_tune_prefill_gemm);
-}
-
-int mi355_qmm_launch(QmmArgs a, int64_t stream) {
-    {   // images staged WITHOUT backing activations (fused MoE staging) may only be consumed by the grouped 9..32-token launch they were
-        // built for; any other route would read rows nobody wrote.  qw1_launch checks the remaining fields (tile height, k, norm, groups)
-        QmgStream& qs0 = qmg_stream(to_stream(stream));
-        if (qs0.chain.valid && qs0.chain.prestaged && qs0.chain.x == a.x && qs0.chain.st == to_stream(stream) &&
-            !(a.grp_n > 1 && qmg_wide_one_launch(a.B) && a.nseg >= 1 && a.seg[0].type != MI355_GGML_Q8_0)) {
-            qs0.chain.valid = false;
-            mi355_note_error((int)hipErrorInvalidValue);
-            return (int)hipErrorInvalidValue;
-        }
-    }
-    if (a.nseg >= 1 && a.seg[0].type == MI355_GGML_Q8_0) return q8_0_launch(a, to_stream(stream));
-    if (a.K <= 0 || (a.K % 256) || a.B < 0 || a.nseg < 1 || a.nseg > 3) return (int)hipErrorInvalidValue;
-    if (a.B == 0) return 0;
-    for (int s = 0; s < a.nseg; ++s)                            // any Q5_K segment: the launch belongs to qmm_q5k.inc, whatever else it asks for
-        if (a.seg[s].type == MI355_GGML_Q5_K) return q5k_route(a, to_stream(stream));
-    for (int s = 0; s < a.nseg; ++s)
-        if (a.seg[s].type != MI355_GGML_Q4_K && a.seg[s].type != MI355_GGML_Q6_K) return (int)hipErrorInvalidValue;
-    if (a.paired && (a.nseg != 2 || a.seg[0].n_tiles != a.seg[1].n_tiles)) return (int)hipErrorInvalidValue;
-    if (a.grp_n > 1) {
-        // grouped launch: grp_n mat-muls of these shapes.  The 9..32-token path runs them as the z extent of its launches; everything
-        // else (other token counts, the exact modes) runs them one after the other -- same results, the descriptor's meaning is the loop
-        if (a.moe_expert || a.bias || (a.epi != MI355_EPI_STORE && a.epi != MI355_EPI_SILU_MUL)) return (int)hipErrorInvalidValue;
-        const bool one_launch = qmg_wide_one_launch(a.B);
-        if (!one_launch) {
-            const size_t xes = (a.x_dtype == MI355_DTYPE_BF16) ? 2 : 4;
-            for (int e = 0; e < a.grp_n; ++e) {
-                QmmArgs r = a;
-                r.grp_n = 0; r.chain_next = 0;
-                for (int s = 0; s < a.nseg; ++s) r.seg[s].w = a.seg[s].w + (size_t)e * a.moe_stride[s];
-                r.x = static_cast<const uint8_t*>(a.x) + (size_t)e * a.grp_x * xes;
-                r.out = a.out + (size_t)e * a.grp_out;
-                if (a.rows_dev) r.rows_dev = a.rows_dev + e;
-                const int rc = mi355_qmm_launch(r, stream);
-                if (rc) return rc;
-            }
-            return 0;
-        }
-    }
-    if (g_qmm_exact && !a.moe_expert && !a.rows_dev) return qmm_exact_launch(a, to_stream(stream));   // parity mode 2 (tests only)
-    int total_tiles = 0;
-    bool div4 = true, div2 = true;
-    for (int s = 0; s < a.nseg; ++s) {
-        total_tiles += a.seg[s].n_tiles;
-        if (a.seg[s].n_tiles % 4) div4 = false;
-        if (a.seg[s].n_tiles % 2) div2 = false;
-    }
-    // tiles per workgroup: amortise the activation staging but keep >= ~1024 workgroups (4 per CU)
-    int R;
-    if (a.paired) {
-        R = (a.seg[0].n_tiles % 2 == 0 && a.seg[0].n_tiles / 2 >= 1024) ? 4 : 2;
-    } else {
-        R = 1;
-        if (div2 && total_tiles / 2 >= 1024) R = 2;
-        // four Q6_K tiles per workgroup need more than the register file (256 VGPRs + spills once the body is branch-free):
-        // lm_head of Llama-3-8B 108 us with R = 4, 74 us with R = 2
-        bool any_q6 = false;
-        for (int s = 0; s < a.nseg; ++s) any_q6 = any_q6 || a.seg[s].type == MI355_GGML_Q6_K;
-        if (div4 && total_tiles / 4 >= 1024 && !any_q6) R = 4;
-    }
-    const int n_wg = a.paired ? a.seg[0].n_tiles / (R / 2) : total_tiles / R;
-    hipStream_t st = to_stream(stream);
-    int wt = a.seg[0].type;                                   // uniform tile type of the launch, else 0 (mixed)
-    for (int s = 1; s < a.nseg; ++s) if (a.seg[s].type != wt) wt = 0;
-    if (a.moe_expert) {                                       // every (token, slot) pair is a 1-token mat-vec of its own expert
-        if (a.moe_pairs < 1 || a.moe_xdiv < 1 || a.epi == MI355_EPI_QKV_ROPE_CACHE || a.epi == MI355_EPI_RESID) return (int)hipErrorInvalidValue;
-        a.B = 1;
-        return qmm_launch_bt<1>(a, R, wt, n_wg, st);
-    }
-    if (a.blk_tab && !(a.B >= QMP_MIN_TOKENS && g_tune_prefill_gemm == 1)) return (int)hipErrorNotSupported;   // only the prompt GEMM reads a block table
-    if (a.B >= QMP_MIN_TOKENS && g_tune_prefill_gemm) {
-        // prompt step: the hand-written quantised GEMM (qmm_prefill.inc); mi355_set_tuning(6, 0) = stream the weights 32 tokens at a time
-        const int rcq = qpg_launch(a, st);
-        if (rcq != (int)hipErrorNotSupported || a.blk_tab) return rcq;
-    }
-    const int B = a.B;
-    const size_t xes = (a.x_dtype == MI355_DTYPE_BF16) ? 2 : 4;
-    const uint8_t* x0 = static_cast<const uint8_t*>(a.x);
-    float* out0 = a.out;
-    const float* resid0 = a.resid;
-    uint16_t* q0 = a.q_out;
-    const int64_t* pos0 = a.positions;
-    const int64_t* slot0 = a.slot_mapping;
-    for (int b0 = 0; b0 < B;) {
-        int bn = B - b0;
-        if (bn > 8) {                                         // 9..32 tokens: wide kernel, weights read once
-            if (bn > 8 * QMW_MAXMT) bn = 8 * QMW_MAXMT;
-            a.B = bn;
-            a.x = x0 + (size_t)b0 * a.ldx * xes;
-            a.out = out0 ? out0 + (size_t)b0 * a.ldo : nullptr;
-            a.resid = resid0 ? resid0 + (size_t)b0 * a.ldo : nullptr;
-            a.q_out = q0 ? q0 + (size_t)b0 * a.Hq * a.D : nullptr;
-            a.positions = pos0 ? pos0 + b0 : nullptr;
-            a.slot_mapping = slot0 ? slot0 + b0 : nullptr;
-            int rcw;
-            if (!g_tune_exact_act) rcw = bn <= 16 ? qw1_launch<1>(a, st) : qw1_launch<2>(a, st);   // one f16 plane, 16-token m-tiles (default)
-            else if (bn <= 16) rcw = qmg_launch<2>(a, st);                                          // hi + lo planes, 8-token m-tiles ("exact")
-            else if (bn <= 24) rcw = qmg_launch<3>(a, st);
-            else rcw = qmg_launch<4>(a, st);
-            if (rcw) return rcw;
-            b0 += bn;
-            continue;
-        }
-        a.B = bn;
-        a.x = x0 + (size_t)b0 * a.ldx * xes;
-        a.out = out0 ? out0 + (size_t)b0 * a.ldo : nullptr;
-        a.resid = resid0 ? resid0 + (size_t)b0 * a.ldo : nullptr;
-        a.q_out = q0 ? q0 + (size_t)b0 * a.Hq * a.D : nullptr;
-        a.positions = pos0 ? pos0 + b0 : nullptr;
-        a.slot_mapping = slot0 ? slot0 + b0 : nullptr;
-        int rc;
-        if (bn == 1) rc = qmm_launch_bt<1>(a, R, wt, n_wg, st);
-        else if (bn == 2) rc = qmm_launch_bt<2>(a, R, wt, n_wg, st);
-        else if (bn <= 4) rc = qmm_launch_bt<4>(a, R, wt, n_wg, st);
-        else rc = qmm_launch_bt<8>(a, R, wt, n_wg, st);
-        if (rc) return rc;
-        b0 += bn;
-    }
-    return 0;
-}
-
-/* internal (host_model.cpp, grouped experts of a decode step): route ids -> the grouped activation images of the NEXT grouped
- * mi355_qmatmul_fused call on this stream (x = x_key, `rows` tokens, k = hidden, the same norm weight, group_count = n_expert,
- * group_x_stride = cap * hidden), which finds them through the chain state and skips its staging launch; also leaves pos[] and counts[]
- * (mi355_moe_group's outputs).  -4: this configuration does not take the one-launch grouped path -- the caller groups and gathers. */
-extern "C" int mi355_internal_moe_stage_grouped(const float* xs, const int32_t* ids, int32_t pairs, int32_t top_k, int32_t n_expert, int32_t cap,
-                                                int32_t r0, int32_t rows, int32_t hidden, const float* norm_w, int32_t* pos_out,
-                                                int32_t* counts_out, const float* x_key, int32_t row_limit, int64_t stream) {
-    if (!xs || !ids || !pos_out || !counts_out || pairs < 1 || top_k < 1 || n_expert < 2 || cap < pairs || (hidden % 256)) return -4;
-    if (!qmg_wide_one_launch(rows)) return -4;                          // the consumer's own path decision (shared helper)
-    hipStream_t st = to_stream(stream);
-    const int MT = rows <= 16 ? 1 : 2, BP = MT * 16, nkb = hidden / 256;
-    const size_t kbb = qw1_kb_bytes(MT);
-    QmgStream& qs = qmg_stream(st);
-    qs.chain.valid = false;
-    const int cur = qs.cur;
-    const size_t imgb = (kbb * nkb + (size_t)nkb * BP * sizeof(float) + 1023) / 1024 * 1024;
-    void* imgp = nullptr;
-    const int rc = qmg_buf(&imgp, cur ? MI355_SCR_QMM_IMG1 : MI355_SCR_QMM_IMG0, (size_t)n_expert * imgb, st);
-    if (rc) return rc;
-    uint8_t* img = static_cast<uint8_t*>(imgp);
-    float* ssp = reinterpret_cast<float*>(img + kbb * nkb);
-    if (MT == 1)
-        hipLaunchKernelGGL((qw1_prep_moe_kernel<1>), dim3(nkb, 2, n_expert), dim3(256), 0, st, img, ssp, xs, ids, pairs, top_k, n_expert, cap, r0,
-                           hidden, norm_w, kbb, (int64_t)imgb, pos_out, counts_out, row_limit > 0 ? row_limit : cap);
-    else
-        hipLaunchKernelGGL((qw1_prep_moe_kernel<2>), dim3(nkb, 4, n_expert), dim3(256), 0, st, img, ssp, xs, ids, pairs, top_k, n_expert, cap, r0,
-                           hidden, norm_w, kbb, (int64_t)imgb, pos_out, counts_out, row_limit > 0 ? row_limit : cap);
-    qs.chain = QmgChainState{true, x_key, rows, hidden, MT, cur, norm_w, st, 1};
-    qs.chain.grp = n_expert; qs.chain.grp_stride = (int64_t)cap * hidden;
-    qs.chain.prestaged = true;                                          // no activations behind x_key: consume these images or fail
-    return (int)hipGetLastError();
-}
+#include "qmm_q5k.inc"     // Q5_K: its own decode and 9..32-token kernels
 
 // The weighted expert rows added to the residual stream (mi355_moe_scatter_combine's arithmetic, bit for bit) AND the activation image of
 // the next 9..32-token mat-mul that reads the residual stream (the next layer's q|k|v or the lm_head; its RMSNorm weight = next_norm_w):
@@ -2425,6 +1637,134 @@ __global__ void __launch_bounds__(256) moe_scatter_combine_img_kernel(float* __r
         qw1_prep_entry(ch.img, ch.ssp, v, t < B, ch.norm_w, ch.MT, ch.kbb, (int)blockIdx.x, t, (int)threadIdx.x);
     }
 }
+
+// ================================================================================================
+// Host side.  Every launcher and the router mi355_qmm_launch are in qmm_launch.inc; below it only the entry points of the C ABI.
+#include "qmm_launch.inc"
+
+// ------------------------------------------------------------------------------------------------ tuning keys
+void mi355_pa_set_fused(int v);
+void mi355_pa_set_wpb(int v);
+void mi355_pa_set_loop(int v);
+void mi355_dense_set_small(int key, int v);
+extern "C" void mi355_host_set_partition_override(int v);
+extern "C" void mi355_host_set_moe_group(int v);
+void mi355_prefill_set_fp8_generic(int v);
+void mi355_prefill_set_lds(int v);
+// ---- A/B switches.  The library honours exactly ten keys (documented in include/mi355_vllm.h; their defaults live in the table
+// below, which is applied through the same setters at load time, so `mi355_get_tuning` always returns the live value of a key);
+// every other key is ignored.
+static int32_t g_tune_shadow[64];
+static bool g_tune_shadow_set[64];
+static const int32_t kProductTuning[][2] = {{3, 1}, {5, 0}, {6, 1}, {9, 1}, {24, 0}, {30, 0}, {41, 1}, {44, 1}, {47, 1}, {48, 1}};
+static bool tuning_is_product_key(int32_t key) {
+    for (const auto& kv : kProductTuning) if (kv[0] == key) return true;
+    return false;
+}
+static void tuning_apply(int32_t key, int32_t value) {
+    if (key == 3) { mi355_pa_set_fused(value & 15); mi355_pa_set_wpb(value >> 4); }   // merge form | 16 x partitions per workgroup (0 = auto)
+    else if (key == 5) mi355_host_set_partition_override(value);
+    else if (key == 6) g_tune_prefill_gemm = value;
+    else if (key == 9) g_tune_chain = value;
+    else if (key == 24) g_tune_exact_act = value;
+    else if (key == 30) mi355_dense_set_small(30, value);           // bit mask of folded launches switched OFF (dense_gemv.hip)
+    else if (key == 41) mi355_host_set_moe_group(value);
+    else if (key == 44) mi355_pa_set_loop(value);
+    else if (key == 47) { mi355_prefill_set_lds(value & 1); mi355_prefill_set_fp8_generic((value >> 1) & 1); }
+    else if (key == 48) g_tune_qpg_fepi = value;
+}
+namespace {
+struct TuningInit {
+    TuningInit() {
+        for (const auto& kv : kProductTuning) { tuning_apply(kv[0], kv[1]); g_tune_shadow[kv[0]] = kv[1]; g_tune_shadow_set[kv[0]] = true; }
+    }
+} g_tuning_init;
+}
+/* 1 when the library honours `key` (the ten product keys) */
+extern "C" int32_t mi355_tuning_supported(int32_t key) {
+    if (key < 0 || key >= 64) return 0;
+    return tuning_is_product_key(key) ? 1 : 0;
+}
+extern "C" int32_t mi355_get_tuning(int32_t key) {
+    if (key < 0 || key >= 64 || !g_tune_shadow_set[key]) return INT32_MIN;
+    return g_tune_shadow[key];
+}
+extern "C" void mi355_set_tuning(int32_t key, int32_t value) {
+    if (!mi355_tuning_supported(key)) return;                       // any other key is ignored (and stays "never set")
+    g_tune_shadow[key] = value; g_tune_shadow_set[key] = true;
+    tuning_apply(key, value);
+}
+
+/* host layers: merge the stream's partials (mi355_internal_paged_attention_v2_partials) into `out` bf16 [B, H, 128] AND stage the image of
+ * the wide mat-mul that reads `out` next on this stream (x = out, k = H * 128, no norm).  9 <= B <= 32, H even.  -4: not this shape. */
+extern "C" int mi355_internal_pa_stream_reduce_to_image(void* out, const float* tmp_out, const float* max_logits, const float* exp_sums,
+                                                        const uint32_t* context_lens, int32_t B, int32_t H, int32_t W, int32_t slots,
+                                                        int64_t stream) {
+    if (B < 9 || B > 32 || (H & 1) || W < 1 || W > 64 || g_tune_exact_act || !g_tune_chain) return -4;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const int MT = B <= 16 ? 1 : 2, BP = MT * 16, K = H * 128, nkb = K / 256;
+    const size_t kbb = qw1_kb_bytes(MT);
+    QmgStream& qs = qmg_stream(st);
+    const int other = qs.cur ^ 1;
+    QmgImage im;
+    const int rc = qmg_image(im, other, kbb, nkb, BP, 1, st);
+    if (rc) return rc;
+    uint8_t* img = im.img;
+    float* ssp = im.ssp;
+    const dim3 grid(H / 2, BP);
+    if (MT == 1)
+        hipLaunchKernelGGL((pa_stream_reduce_img_kernel<1>), grid, dim3(256), 0, st, static_cast<uint16_t*>(out), tmp_out, max_logits, exp_sums,
+                           context_lens, B, H, W, slots, img, ssp, kbb);
+    else
+        hipLaunchKernelGGL((pa_stream_reduce_img_kernel<2>), grid, dim3(256), 0, st, static_cast<uint16_t*>(out), tmp_out, max_logits, exp_sums,
+                           context_lens, B, H, W, slots, img, ssp, kbb);
+    QmgChainState cs{true, out, B, K, MT, other, nullptr, st, 1};
+    cs.x_dtype = MI355_DTYPE_BF16;
+    qs.chain = cs;
+    return (int)hipGetLastError();
+}
+
+extern "C" void mi355_internal_qmm_set_exact(int32_t on) {
+    g_qmm_exact = on ? 1 : 0;
+    // an exact launch stages no activation image for its successor: forget every chain hint, in both directions of the switch
+    std::lock_guard<std::mutex> lk(g_qmg_mu);
+    for (auto& kv : g_qmg_streams) kv.second.chain.valid = false;
+}
+extern "C" int32_t mi355_internal_qmm_get_exact(void) { return g_qmm_exact; }
+
+/* internal (host_model.cpp, grouped experts of a decode step): route ids -> the grouped activation images of the NEXT grouped
+ * mi355_qmatmul_fused call on this stream (x = x_key, `rows` tokens, k = hidden, the same norm weight, group_count = n_expert,
+ * group_x_stride = cap * hidden), which finds them through the chain state and skips its staging launch; also leaves pos[] and counts[]
+ * (mi355_moe_group's outputs).  -4: this configuration does not take the one-launch grouped path -- the caller groups and gathers. */
+extern "C" int mi355_internal_moe_stage_grouped(const float* xs, const int32_t* ids, int32_t pairs, int32_t top_k, int32_t n_expert, int32_t cap,
+                                                int32_t r0, int32_t rows, int32_t hidden, const float* norm_w, int32_t* pos_out,
+                                                int32_t* counts_out, const float* x_key, int32_t row_limit, int64_t stream) {
+    if (!xs || !ids || !pos_out || !counts_out || pairs < 1 || top_k < 1 || n_expert < 2 || cap < pairs || (hidden % 256)) return -4;
+    if (!qmg_wide_one_launch(rows)) return -4;                          // the consumer's own path decision (shared helper)
+    hipStream_t st = to_stream(stream);
+    const int MT = rows <= 16 ? 1 : 2, BP = MT * 16, nkb = hidden / 256;
+    const size_t kbb = qw1_kb_bytes(MT);
+    QmgStream& qs = qmg_stream(st);
+    qs.chain.valid = false;
+    const int cur = qs.cur;
+    QmgImage im;
+    const int rc = qmg_image(im, cur, kbb, nkb, BP, n_expert, st);
+    if (rc) return rc;
+    uint8_t* img = im.img;
+    float* ssp = im.ssp;
+    const size_t imgb = im.stride;
+    if (MT == 1)
+        hipLaunchKernelGGL((qw1_prep_moe_kernel<1>), dim3(nkb, 2, n_expert), dim3(256), 0, st, img, ssp, xs, ids, pairs, top_k, n_expert, cap, r0,
+                           hidden, norm_w, kbb, (int64_t)imgb, pos_out, counts_out, row_limit > 0 ? row_limit : cap);
+    else
+        hipLaunchKernelGGL((qw1_prep_moe_kernel<2>), dim3(nkb, 4, n_expert), dim3(256), 0, st, img, ssp, xs, ids, pairs, top_k, n_expert, cap, r0,
+                           hidden, norm_w, kbb, (int64_t)imgb, pos_out, counts_out, row_limit > 0 ? row_limit : cap);
+    qs.chain = QmgChainState{true, x_key, rows, hidden, MT, cur, norm_w, st, 1};
+    qs.chain.grp = n_expert; qs.chain.grp_stride = (int64_t)cap * hidden;
+    qs.chain.prestaged = true;                                          // no activations behind x_key: consume these images or fail
+    return (int)hipGetLastError();
+}
+
 /* internal (host_model.cpp): -4 = this configuration does not chain (the caller runs mi355_moe_scatter_combine) */
 extern "C" int mi355_internal_moe_scatter_combine_to_image(float* ys, const float* y_rows, const float* weights, const int32_t* inv, int32_t num_tokens,
                                                            int32_t hidden, int32_t top_k, const float* next_norm_w, int64_t stream) {
@@ -2436,11 +1776,10 @@ extern "C" int mi355_internal_moe_scatter_combine_to_image(float* ys, const floa
     QmgStream& qs = qmg_stream(st);
     qs.chain.valid = false;
     const int other = qs.cur ^ 1;
-    void* imgp = nullptr;
-    const int rc = qmg_buf(&imgp, other ? MI355_SCR_QMM_IMG1 : MI355_SCR_QMM_IMG0, kbb * nkb + (size_t)nkb * BP * sizeof(float), st);
+    QmgImage im;
+    const int rc = qmg_image(im, other, kbb, nkb, BP, 1, st);
     if (rc) return rc;
-    uint8_t* img = static_cast<uint8_t*>(imgp);
-    const QmgChainOut ch{img, reinterpret_cast<float*>(img + kbb * nkb), next_norm_w, hidden, MT, kbb, 1};
+    const QmgChainOut ch{im.img, im.ssp, next_norm_w, hidden, MT, kbb, 1};
     hipLaunchKernelGGL(moe_scatter_combine_img_kernel, dim3(nkb, BP), dim3(256), 0, st, ys, y_rows, weights, inv, hidden, top_k, num_tokens, ch);
     qs.chain = QmgChainState{true, ys, num_tokens, hidden, MT, other, next_norm_w, st, 1};
     return (int)hipGetLastError();

@@ -1,4 +1,5 @@
-// Q5_K (GGML type 13, the Q5_K_M mix) on the quantised mat-mul path.   Included by qmatmul.hip after the shared helpers.
+// Q5_K (GGML type 13, the Q5_K_M mix) on the quantised mat-mul path: device code only.  Included by qmatmul.hip after the shared device
+// helpers; the launchers (q5k_launch_btrm, q5g_launch) and the routing are in qmm_launch.inc.
 //
 // Reference boundary: candle `QMatMul::forward` over a Q5K tensor (SURVEY App. C), same call sites as Q4_K / Q6_K.
 // block_q5_K = f16 d, dmin | scales[12] (6-bit sc_j, m_j as Q4_K) | qh[32] | qs[128];  w = d sc_j q - dmin m_j with
@@ -20,7 +21,7 @@
 //     eight row tiles per workgroup and ALL of them compute: the next k-block's image travels global -> registers -> LDS
 //     (each wave copies its 1-KiB chunks while it multiplies; two LDS stages, one barrier per k-block), split K,
 //     partial sums [ks][token][row] finished by qmm_epilogue_kernel (every epilogue of the path).
-// Not served (hipErrorNotSupported, nothing computed): MoE expert ids, grouped launches, block tables, parity mode 2.
+// Not served (mi355_qmm_launch: hipErrorNotSupported, nothing computed): MoE expert ids, grouped launches, block tables, parity mode 2.
 
 typedef unsigned int q5k_u32x2_t __attribute__((ext_vector_type(2)));
 
@@ -366,132 +367,4 @@ __global__ void __launch_bounds__(512) q5g_gemm_kernel(const QmmArgs a, const ui
 #pragma unroll
             for (int v = 0; v < 4; ++v) pp[(size_t)(16 * mt + 4 * kg + v) * ldp] = y[mt][v];
     }
-}
-
-// ================================================================================================ host side
-// MT = m-tiles of 16 tokens (1: 9..16 tokens, 2: 17..32); every segment Q5_K
-template <int MT>
-static int q5g_launch(const QmmArgs& a0, hipStream_t st) {
-    QmmArgs a = a0;
-    a.paired = 0;                                   // slots are plain (segment, tile) order; the epilogue pairs gate / up rows
-    a.chain_next = 0;
-    const int nkb = a.K / 256, BP = MT * 16;
-    int n_slots = 0;
-    for (int s = 0; s < a.nseg; ++s) n_slots += a.seg[s].n_tiles;
-    const int ldp = n_slots * 16;
-    const size_t kbb = qw1_kb_bytes(MT);
-    int ks = 1;
-    while (n_slots * ks < QMG_KS_TARGET && nkb / (ks * 2) >= QMG_KS_MINKB) ks *= 2;
-    {   // no empty split
-        const int kb_per = (nkb + ks - 1) / ks;
-        ks = (nkb + kb_per - 1) / kb_per;
-    }
-    QmgStream& qs = qmg_stream(st);
-    void* imgp = nullptr;
-    int rc = qmg_buf(&imgp, qs.cur ? MI355_SCR_QMM_IMG1 : MI355_SCR_QMM_IMG0, kbb * nkb + (size_t)nkb * BP * sizeof(float), st);
-    if (rc) return rc;
-    void* partp = nullptr;
-    rc = qmg_buf(&partp, MI355_SCR_QMM_PART, (size_t)ks * BP * ldp * sizeof(float), st);
-    if (rc) return rc;
-    uint8_t* img = static_cast<uint8_t*>(imgp);
-    float* ssp = reinterpret_cast<float*>(img + kbb * nkb);                 // [nkb][BP] after the image
-    float* part = static_cast<float*>(partp);
-    hipLaunchKernelGGL((qw1_prep_kernel<MT>), dim3(nkb, MT * 2), dim3(256), 0, st, img, ssp, a, kbb);
-    hipLaunchKernelGGL((q5g_gemm_kernel<MT>), dim3((n_slots + Q5G_NC - 1) / Q5G_NC, ks), dim3(64 * Q5G_NC), 2 * kbb, st, a, img, part, ldp, n_slots);
-    hipLaunchKernelGGL(qmm_epilogue_kernel, dim3((ldp + 255) / 256, a.B), dim3(256), 0, st, a, part, ldp, ks, BP, ssp,
-                       QmgChainOut{nullptr, nullptr, nullptr, 0, 0, 0, 0}, (const float*)nullptr);
-    return (int)hipGetLastError();
-}
-
-// waves per workgroup: the largest of 8 / 4 / 2 that leaves every workgroup of the launch resident at once (qmm_pick_nw's rule)
-template <int BT, int R, bool MIXED>
-static int q5k_launch_decode(QmmArgs& a, int n_wg, hipStream_t st) {
-    static Mi355DevOnce attr_done;
-    static int blocks_per_cu[3] = {-1, -1, -1};
-    if (!attr_done.done()) {
-        (void)hipFuncSetAttribute((const void*)q5k_kernel<BT, R, MIXED>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr_done.set();
-    }
-    const int nkb = a.K / 256, cus = mi355_num_cus();
-    int NW = 1, fits = 0;
-    for (int i = 0; i < 3 && !fits; ++i) {
-        const int nw = 8 >> i;
-        if (nw > nkb) continue;
-        if (blocks_per_cu[i] < 0) {
-            int nb = 0;
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)q5k_kernel<BT, R, MIXED>, 64 * nw, qmm_lds_bytes(BT, R, nw)) != hipSuccess || nb < 1) nb = 1;
-            blocks_per_cu[i] = nb;
-        }
-        NW = nw;
-        fits = (long)n_wg <= (long)blocks_per_cu[i] * cus;
-    }
-    if (!fits && nkb >= 4) NW = 4;                      // several rounds of workgroups anyway
-    const size_t shm = qmm_lds_bytes(BT, R, NW);
-    if (shm > 160 * 1024) return (int)hipErrorInvalidValue;
-    hipLaunchKernelGGL((q5k_kernel<BT, R, MIXED>), dim3(n_wg), dim3(64 * NW), shm, st, a);
-    return (int)hipGetLastError();
-}
-template <int BT>
-static int q5k_launch_bt(QmmArgs& a, int R, bool mixed, int n_wg, hipStream_t st) {
-    if (R == 2) return mixed ? q5k_launch_decode<BT, 2, true>(a, n_wg, st) : q5k_launch_decode<BT, 2, false>(a, n_wg, st);
-    return mixed ? q5k_launch_decode<BT, 1, true>(a, n_wg, st) : q5k_launch_decode<BT, 1, false>(a, n_wg, st);
-}
-
-// Fewest tokens of a Q5_K launch that take the prompt-step GEMM.  Above QMP_MIN_TOKENS (96) because the chunked path below splits K and the
-// prompt GEMM does not: the Llama-3-8B down projection (4096 x 14336: 16 row blocks, 56 k-blocks in a row) takes 184..186 us from 96 to 256
-// tokens on the GEMM against 35.5 us per 32-token chunk (107 us at 96, 142 us at 128 tokens) -- it wins from the sixth chunk on, gate|up
-// (67 against 132 us at 96 tokens) from the start.  DESIGN.md section 5b has the table.
-#define Q5P_MIN_TOKENS 192
-// every launch with a Q5_K segment (mi355_qmm_launch has validated K, B > 0 and the segment count)
-static int q5k_route(QmmArgs a, hipStream_t st) {
-    bool pure = true, div2 = true;
-    int total_tiles = 0;
-    for (int s = 0; s < a.nseg; ++s) {
-        if (!is_kquant(a.seg[s].type)) return (int)hipErrorInvalidValue;
-        pure = pure && a.seg[s].type == MI355_GGML_Q5_K;
-        total_tiles += a.seg[s].n_tiles;
-        if (a.seg[s].n_tiles % 2) div2 = false;
-    }
-    // the expert, grouped and block-table kernels and the parity-mode kernel decode Q4_K / Q6_K only: refuse, never mis-decode
-    if (a.moe_expert || a.grp_n > 1 || a.blk_tab || g_qmm_exact) return (int)hipErrorNotSupported;
-    if (a.paired && (a.nseg != 2 || a.seg[0].n_tiles != a.seg[1].n_tiles)) return (int)hipErrorInvalidValue;
-    qmg_stream(st).chain.valid = false;                 // no activation image is staged for a successor
-    if (a.B >= Q5P_MIN_TOKENS && g_tune_prefill_gemm) {
-        // prompt step: the Q5_K arms of the prompt-step GEMM (qmm_prefill.inc), one GEMM per run of segments of one type;
-        // mi355_set_tuning(6, 0) = the 32-token chunks below (A/B)
-        const int rcq = qpg_launch(a, st);
-        if (rcq != (int)hipErrorNotSupported) return rcq;
-    }
-    // tiles per workgroup: two amortise the activation staging where >= ~4 workgroups per CU remain; gate / up pairs are two by construction
-    const int R = a.paired ? 2 : ((div2 && total_tiles / 2 >= 1024) ? 2 : 1);
-    const int n_wg = a.paired ? a.seg[0].n_tiles : total_tiles / R;
-    const int B = a.B;
-    const size_t xes = (a.x_dtype == MI355_DTYPE_BF16) ? 2 : 4;
-    const uint8_t* x0 = static_cast<const uint8_t*>(a.x);
-    float* out0 = a.out;
-    const float* resid0 = a.resid;
-    uint16_t* q0 = a.q_out;
-    const int64_t* pos0 = a.positions;
-    const int64_t* slot0 = a.slot_mapping;
-    for (int b0 = 0; b0 < B;) {
-        // 9 tokens and up: the GEMM kernel, 32 tokens per launch -- launches that mix in other types stay on the 8-token kernel
-        const int left = B - b0, bn = (pure && left > 8) ? (left > 32 ? 32 : left) : (left > 8 ? 8 : left);
-        a.B = bn;
-        a.x = x0 + (size_t)b0 * a.ldx * xes;
-        a.out = out0 ? out0 + (size_t)b0 * a.ldo : nullptr;
-        a.resid = resid0 ? resid0 + (size_t)b0 * a.ldo : nullptr;
-        a.q_out = q0 ? q0 + (size_t)b0 * a.Hq * a.D : nullptr;
-        a.positions = pos0 ? pos0 + b0 : nullptr;
-        a.slot_mapping = slot0 ? slot0 + b0 : nullptr;
-        int rc;
-        if (bn > 16) rc = q5g_launch<2>(a, st);
-        else if (bn > 8) rc = q5g_launch<1>(a, st);
-        else if (bn == 1) rc = q5k_launch_bt<1>(a, R, !pure, n_wg, st);
-        else if (bn == 2) rc = q5k_launch_bt<2>(a, R, !pure, n_wg, st);
-        else if (bn <= 4) rc = q5k_launch_bt<4>(a, R, !pure, n_wg, st);
-        else rc = q5k_launch_bt<8>(a, R, !pure, n_wg, st);
-        if (rc) return rc;
-        b0 += bn;
-    }
-    return 0;
 }

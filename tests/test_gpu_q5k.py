@@ -178,6 +178,61 @@ def test_refusals_compute_nothing(cv, lib, what):
     assert rc == 801 and bool((out == -7.0).all())
 
 
+@pytest.mark.parametrize("what,B,windows", [("q4k_resid", 41, (32, 9)), ("q5k_silu_pair", 41, (32, 9)), ("mixed_qkv_rope_cache", 19, (8, 8, 3))])
+def test_one_call_equals_calls_on_its_token_windows(cv, what, B, windows):
+    """One mi355_qmatmul_fused call of B tokens is cut into windows of tokens: 32, then 9..32 for Q4_K / Q6_K and for pure Q5_K launches,
+    8-token windows where Q5_K is mixed with other types.  Tiles per workgroup, waves and the k-split do not depend on B, so the
+    sub-launches are the same launches as separate calls on those windows: every output must be BIT-identical.  Distinct positions and
+    slots: a window whose positions / slot_mapping / q_out offset is off writes other cache slots or rotates by another angle.
+    (ops.qmatmul_fused never requests a chain: chain_next = 0 throughout.)"""
+    assert sum(windows) == B
+    rng = np.random.default_rng(41)
+    K, N = 512, 64
+    q4 = lambda: cv.QMatMul(kq.quantize(rng.normal(0, 0.05, (N, K)).astype(np.float32), kq.GGML_Q4_K), kq.GGML_Q4_K, "cuda")
+    q6 = lambda: cv.QMatMul(kq.quantize(rng.normal(0, 0.05, (N, K)).astype(np.float32), kq.GGML_Q6_K), kq.GGML_Q6_K, "cuda")
+    q5 = lambda salt: cv.QMatMul(case(N, K, salt=salt)[0], Q5, "cuda")
+    x = dev(rng.normal(size=(B, K)).astype(np.float32))
+    starts = np.concatenate([[0], np.cumsum(windows)[:-1]])
+
+    if what != "mixed_qkv_rope_cache":
+        mats = [q4()] if what == "q4k_resid" else [q5(0), q5(1)]
+        epi = cv.EPI_RESID if what == "q4k_resid" else cv.EPI_SILU_MUL
+        res = dev(rng.normal(size=(B, N)).astype(np.float32))
+
+        def run(lo, hi, out):
+            cv.qmatmul_fused(mats, x[lo:hi], epilogue=epi, out=out[lo:hi], residual=res[lo:hi] if epi == cv.EPI_RESID else None)
+        whole, parts = (torch.full((B, N), -7.0, dtype=torch.float32, device="cuda") for _ in range(2))
+        run(0, B, whole)
+        for b0, bn in zip(starts, windows):
+            run(int(b0), int(b0 + bn), parts)
+        torch.cuda.synchronize()
+        assert np.isfinite(whole.cpu().numpy()).all() and not bool((whole == -7.0).any())
+        assert torch.equal(whole, parts)
+        return
+
+    mats = [q5(0), q4(), q6()]                                          # q (Q5_K) | k (Q4_K) | v (Q6_K): the 8-token mixed kernel
+    H, Hkv, D, bs, NB = 1, 1, 64, 64, 2
+    nw = dev((1 + rng.normal(0, 0.1, K)).astype(np.float32))
+    pos = dev(rng.permutation(500)[:B].astype(np.int64))
+    slots = dev(rng.permutation(NB * bs)[:B].astype(np.int64))
+    cos, sin = (dev(t) for t in O.rope_tables(500000.0, D, 512))
+    ks, vs = O.kv_cache_shapes(NB, bs, Hkv, D, 2, True)
+    kc0, vc0 = rng.integers(0, 65536, ks).astype(np.uint16), rng.integers(0, 65536, vs).astype(np.uint16)
+    got = []
+    for cuts in ([(0, B)], [(int(b0), int(b0 + bn)) for b0, bn in zip(starts, windows)]):
+        kcd, vcd = (dev(c.view(np.int16)).view(torch.bfloat16) for c in (kc0, vc0))
+        q_out = torch.zeros((B, H * D), dtype=torch.bfloat16, device="cuda")
+        for lo, hi in cuts:
+            cv.qmatmul_fused(mats, x[lo:hi], epilogue=cv.EPI_QKV_ROPE_CACHE, norm_weight=nw, norm_eps=1e-5,
+                             rope=dict(cos=cos, sin=sin, positions=pos[lo:hi], slot_mapping=slots[lo:hi], q_out=q_out[lo:hi],
+                                       key_cache=kcd, value_cache=vcd, num_heads=H, num_kv_heads=Hkv, head_dim=D))
+        torch.cuda.synchronize()
+        got.append([t.view(torch.int16).cpu().numpy() for t in (q_out, kcd, vcd)])
+    assert (got[0][1] != kc0.view(np.int16)).sum() > B * Hkv * D // 2 and bool(got[0][0].any())   # the call did write the cache and q
+    for a, b in zip(*got):
+        assert np.array_equal(a, b)
+
+
 def test_q5km_model_file(lib, tmp_path):
     """the tiny Q4_K_M Llama with every Q4_K tensor re-encoded as Q5_K (zero fifth bits: bit-identical weights, so the oracle
     on the original weights is exact): a 24-token prompt step, then 8 greedy steps, eager and as a replayed graph"""
