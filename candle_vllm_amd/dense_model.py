@@ -96,6 +96,16 @@ class DenseLlama:
         _check(lib.mi355_dense_set_gptq(self.h, layer, W_SLOTS[name], qw.ctypes.data, sc.ctypes.data, n, k, group_size),
                f"set_gptq {name}")
 
+    def set_fp8(self, layer, name, w_u8, scale_f32):
+        """`LnFp8` projection (linear.rs:918-1221): w [n, k] e4m3fn bytes, scale [ceil(n/128), k/128] f32 (`weight_scale` /
+        `weight_scale_inv`), block size 128 x 128"""
+        w = np.ascontiguousarray(w_u8, np.uint8)
+        sc = np.ascontiguousarray(scale_f32, np.float32)
+        n, k = w.shape
+        if sc.shape != (-(-n // 128), -(-k // 128)):
+            raise ValueError(f"set_fp8 {name}: scale shape {sc.shape} does not match a [{n}, {k}] weight in 128 x 128 blocks")
+        _check(lib.mi355_dense_set_fp8(self.h, layer, W_SLOTS[name], w.ctypes.data, sc.ctypes.data, n, k), f"set_fp8 {name}")
+
     def load_oracle_weights(self, W):
         for name in ("tok_embd", "output_norm", "output", "output_norm_b"):
             if name in W:

@@ -622,6 +622,36 @@ class GPTQLinear:
         return out
 
 
+class Fp8Linear:
+    """`LnFp8` (linear.rs:918-1221): weight [out, in] e4m3fn bytes (uint8) + one f32 scale per 128 x 128 block (`weight_scale` /
+    `weight_scale_inv`, [ceil(out/128), in/128]); re-ordered into the tile image at construction (out % 16 == 0, in % 128 == 0).
+    W8A16: 16-bit activations, exact weights, f32 accumulation; the decode epilogues fused as in `Linear`."""
+
+    def __init__(self, weight_u8, weight_scale, bias=None, block_size=(128, 128)):
+        if weight_u8.dtype != torch.uint8 or weight_scale.dtype != torch.float32:
+            raise RuntimeError("Fp8Linear takes uint8 e4m3fn bytes and f32 block scales")
+        self.n, self.k = weight_u8.shape
+        self.block_n, self.block_k = block_size
+        if tuple(weight_scale.shape) != (-(-self.n // self.block_n), -(-self.k // self.block_k)):
+            raise RuntimeError("weight_scale must be [ceil(out / block), ceil(in / block)]")
+        self.scale, self.bias = weight_scale.contiguous(), bias
+        weight_u8 = weight_u8.contiguous()                     # the repack reads [n][k] row-major through the raw pointer
+        self.weight = torch.empty_like(weight_u8)
+        _check(lib.mi355_fp8_tile_repack(_dev(weight_u8), _dev(self.weight), self.n, self.k, _stream()), "fp8_tile_repack")
+
+    def forward(self, x, *, epilogue=EPI_STORE, residual=None, out=None):
+        x2 = x.reshape(-1, self.k)
+        T = x2.shape[0]
+        n_out = self.n // 2 if epilogue == EPI_SILU_MUL else self.n
+        if out is None:
+            out = torch.empty((T, n_out), dtype=x.dtype, device=x.device)
+        _check(lib.mi355_fp8_linear_tiled(_dev(out), _dev(x2), _dev(self.weight), _dev(self.scale),
+                                          _dev(self.bias) if self.bias is not None else None,
+                                          _dev(residual) if residual is not None else None, T, self.n, self.k,
+                                          self.block_n, self.block_k, _DT[x.dtype], epilogue, _stream()), "fp8_linear")
+        return out
+
+
 def rope_tables(rope_theta, rotary_dim, max_seq_len, scaling=None, max_position_embeddings=0):
     """`ScalingRotaryEmbedding::new` (layers/rotary_emb.rs:107-341): cos, sin f32 [n, rotary_dim/2] built by the
     library's host code.  scaling: None or a `_lib.RopeScaling`."""

@@ -423,6 +423,21 @@ int mi355_gptq_tile_repack(const void* in, void* out, int32_t k, int32_t n_in, i
 int mi355_gptq_tile_unpack(const void* in, void* out, int32_t k, int32_t n, int64_t stream);
 /* host helper: word index of qweight[kr][n] inside the tiled image of a [k/8][n_total] tensor (-1 when the shape is not tiled) */
 int64_t mi355_gptq_tile_index(int32_t kr, int32_t n, int32_t k, int32_t n_total);
+/* `LnFp8::forward` (linear.rs:918-1221; selected at :1326-1352, :1454-1497): block-scaled FP8 checkpoints.  w is [n, k] OCP e4m3fn
+ * bytes with one f32 scale per 128 x 128 block, w_scale [ceil(n/128)][k/128] in checkpoint order (`weight_scale` or
+ * `weight_scale_inv`: the same tensor):  out = x . (e4m3(w) * scale)^T (+bias), x / out / bias / residual in `dtype` (BF16 / F16).
+ * W8A16: the weight bytes are decoded exactly, the activations are not quantised, accumulation is f32 with the scale applied in f32
+ * per (row block, 128 k); epilogues and rounding points as mi355_linear (SILU_MUL: w is the packed [gate; up] matrix, n % 32 == 0, and
+ * w_scale the scale rows of that packed matrix).  Served: n % 16 == 0 (n need not be a multiple of 128: the last scale row covers a
+ * ragged block), k % 128 == 0, block_n == block_k == 128; anything else returns hipErrorNotSupported / hipErrorInvalidValue before any
+ * launch.  The NaN codes 0x7f / 0xff decode to NaN.
+ * mi355_fp8_tile_repack (linear.rs:918-1221, load time): checkpoint bytes [n][k] -> the tile image the kernels stream, byte (n, k) at
+ *   ((((n/16) * (k_total/128) + k/128) * 2 + (k%128)/64) * 64 + 16 * ((k%32)/8) + n%16) * 16 + 8 * ((k%64)/32) + k%8
+ * -- 16-row x 128-k tiles of 2 KiB in MFMA B-fragment order, a wave's loads whole contiguous KiB; device to device, in != out. */
+int mi355_fp8_tile_repack(const void* in, void* out, int32_t n, int32_t k, int64_t stream);
+int mi355_fp8_linear_tiled(void* out, const void* x, const void* w_tiled, const float* w_scale,
+                           const void* bias, const void* residual, int32_t num_tokens, int32_t n, int32_t k,
+                           int32_t block_n, int32_t block_k, int32_t dtype, int32_t epilogue, int64_t stream);
 
 /* RoPE cos/sin table builders (HOST): DefaultRotaryEmbedding::new / ScalingRotaryEmbedding::new
  * (layers/rotary_emb.rs:14-48,107-341,358-457) in the reference's f32 arithmetic.  Tables are f32
@@ -623,6 +638,12 @@ int mi355_dense_set_weight_dev(void* model, int32_t layer, int32_t which, const 
  * 16-bit [k/g, n] from the HOST in checkpoint order; sym, no act-order (the Marlin-eligible case, linear.rs:319-325) */
 int mi355_dense_set_gptq(void* model, int32_t layer, int32_t which, const void* qweight_host, const void* scales_host,
                          int32_t n, int32_t k, int32_t group_size);
+/* FP8 projection (`LnFp8`, linear.rs:918-1221) instead of a dense one: w e4m3fn bytes [n, k], scale f32 [ceil(n/128)][k/128] from the
+ * HOST in checkpoint order, block size 128 x 128; slots MI355_W_WQ .. MI355_W_W3 (gate and up are packed along n, their scale rows
+ * stacked).  n % 16 == 0, k % 128 == 0; refused after mi355_dense_finalize.  Under tensor parallelism the tensors are this rank's
+ * shards as given (scale rows are not re-sliced). */
+int mi355_dense_set_fp8(void* model, int32_t layer, int32_t which, const void* w_host, const float* scale_host,
+                        int32_t n, int32_t k);
 /* tensor parallel (distributed.rs:243-249,492-534,696-711,1632-1667): comm from mi355_comm_create (borrowed);
  * all-reduce of the 16-bit stream after o_proj / down_proj, vocab-parallel lm_head + all-gather */
 int mi355_dense_set_comm(void* model, void* comm);
