@@ -106,6 +106,16 @@ class DenseLlama:
             raise ValueError(f"set_fp8 {name}: scale shape {sc.shape} does not match a [{n}, {k}] weight in 128 x 128 blocks")
         _check(lib.mi355_dense_set_fp8(self.h, layer, W_SLOTS[name], w.ctypes.data, sc.ctypes.data, n, k), f"set_fp8 {name}")
 
+    def set_mxfp4(self, layer, name, blocks_u8, scales_u8):
+        """`LnMxfp4` projection (linear.rs:1677-1757): blocks [n, k/2] uint8 (two e2m1 codes per byte, low nibble first), scales
+        [n, k/32] uint8 e8m0"""
+        b = np.ascontiguousarray(blocks_u8, np.uint8)
+        sc = np.ascontiguousarray(scales_u8, np.uint8)
+        n, k = b.shape[0], b.shape[1] * 2
+        if sc.shape != (n, k // 32) or k % 32:
+            raise ValueError(f"set_mxfp4 {name}: scale shape {sc.shape} does not match [{n}, {k}] weights in groups of 32")
+        _check(lib.mi355_dense_set_mxfp4(self.h, layer, W_SLOTS[name], b.ctypes.data, sc.ctypes.data, n, k), f"set_mxfp4 {name}")
+
     def load_oracle_weights(self, W):
         for name in ("tok_embd", "output_norm", "output", "output_norm_b"):
             if name in W:

@@ -652,6 +652,36 @@ class Fp8Linear:
         return out
 
 
+class Mxfp4Linear:
+    """`LnMxfp4` (linear.rs:1677-1757): blocks [out, in/2] uint8 (two e2m1 codes per byte, low nibble first: `blocks` /
+    `weight_packed`) + e8m0 scales [out, in/32] uint8 (`scales` / `weight_scale`); re-ordered into the tile image at construction
+    (out % 16 == 0, in % 128 == 0).  W4A16: 16-bit activations, exact weights, f32 accumulation; the decode epilogues fused as in `Linear`."""
+
+    def __init__(self, blocks_u8, scales_u8, bias=None):
+        if blocks_u8.dtype != torch.uint8 or scales_u8.dtype != torch.uint8:
+            raise RuntimeError("Mxfp4Linear takes uint8 e2m1 blocks and uint8 e8m0 scales")
+        self.n, self.k = blocks_u8.shape[0], blocks_u8.shape[1] * 2
+        if tuple(scales_u8.shape) != (self.n, self.k // 32) or self.k % 32:
+            raise RuntimeError("scales must be [out, in / 32]")
+        self.bias = bias
+        blocks_u8, scales_u8 = blocks_u8.contiguous(), scales_u8.contiguous()   # the repack reads row-major through the raw pointers
+        self.weight, self.scale = torch.empty_like(blocks_u8), torch.empty_like(scales_u8)
+        _check(lib.mi355_mxfp4_tile_repack(_dev(blocks_u8), _dev(scales_u8), _dev(self.weight), _dev(self.scale), self.n, self.k,
+                                           _stream()), "mxfp4_tile_repack")
+
+    def forward(self, x, *, epilogue=EPI_STORE, residual=None, out=None):
+        x2 = x.reshape(-1, self.k)
+        T = x2.shape[0]
+        n_out = self.n // 2 if epilogue == EPI_SILU_MUL else self.n
+        if out is None:
+            out = torch.empty((T, n_out), dtype=x.dtype, device=x.device)
+        _check(lib.mi355_mxfp4_linear_tiled(_dev(out), _dev(x2), _dev(self.weight), _dev(self.scale),
+                                            _dev(self.bias) if self.bias is not None else None,
+                                            _dev(residual) if residual is not None else None, T, self.n, self.k,
+                                            32, _DT[x.dtype], epilogue, _stream()), "mxfp4_linear")
+        return out
+
+
 def rope_tables(rope_theta, rotary_dim, max_seq_len, scaling=None, max_position_embeddings=0):
     """`ScalingRotaryEmbedding::new` (layers/rotary_emb.rs:107-341): cos, sin f32 [n, rotary_dim/2] built by the
     library's host code.  scaling: None or a `_lib.RopeScaling`."""

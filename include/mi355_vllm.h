@@ -438,6 +438,24 @@ int mi355_fp8_tile_repack(const void* in, void* out, int32_t n, int32_t k, int64
 int mi355_fp8_linear_tiled(void* out, const void* x, const void* w_tiled, const float* w_scale,
                            const void* bias, const void* residual, int32_t num_tokens, int32_t n, int32_t k,
                            int32_t block_n, int32_t block_k, int32_t dtype, int32_t epilogue, int64_t stream);
+/* `LnMxfp4::forward` (linear.rs:1677-1757; selected at :1355-1372, :1500-1523): MXFP4 checkpoints (OCP MX v1.0).  blocks is [n, k/2]
+ * bytes -- byte j of a row holds element 2j in its LOW nibble and 2j + 1 in its high nibble; a nibble is sign (bit 3) | index into
+ * {0, 0.5, 1, 1.5, 2, 3, 4, 6} -- and scales is [n, k/32] e8m0 bytes (2^(code - 127)), one per 32 k:
+ *   out = x . (e2m1(blocks) * 2^(scales - 127))^T (+bias), x / out / bias / residual in `dtype` (BF16 / F16).
+ * W4A16: the weights are decoded exactly for scale codes 2..250, the activations are not quantised, accumulation is f32; epilogues and
+ * rounding points as mi355_linear (SILU_MUL: the image is that of the packed [gate; up] matrix, n % 32 == 0).  A scale code 0xFF makes
+ * the outputs of its row NaN; codes 0, 1, 251..254 run clean with no promise on the value.  Served: n % 16 == 0, k % 128 == 0,
+ * group == 32; anything else returns hipErrorNotSupported / hipErrorInvalidValue before any launch.
+ * mi355_mxfp4_tile_repack (linear.rs:1677-1757, load time): checkpoint tensors -> the two planes the kernels stream, device to device,
+ * in != out.  Block byte (n, j) (elements k = 2j, 2j + 1) goes to byte
+ *   (((n/16) * (k_total/128) + k/128) * 64 + 16 * ((k%32)/8) + n%16) * 16 + 4 * ((k%128)/32) + (k%8)/2        of out_tiles (n * k/2 bytes)
+ * -- 16-row x 128-k tiles of 1 KiB in MFMA B-fragment order, a wave's loads whole contiguous KiB -- and scale byte (n, g = k/32) to byte
+ *   (((n/16) * (k_total/128) + g/4) * 16 + n%16) * 4 + g%4                                                    of out_scales (n * k/32 bytes). */
+int mi355_mxfp4_tile_repack(const void* in_blocks, const void* in_scales, void* out_tiles, void* out_scales,
+                            int32_t n, int32_t k, int64_t stream);
+int mi355_mxfp4_linear_tiled(void* out, const void* x, const void* w_tiled, const void* s_tiled,
+                             const void* bias, const void* residual, int32_t num_tokens, int32_t n, int32_t k,
+                             int32_t group, int32_t dtype, int32_t epilogue, int64_t stream);
 
 /* RoPE cos/sin table builders (HOST): DefaultRotaryEmbedding::new / ScalingRotaryEmbedding::new
  * (layers/rotary_emb.rs:14-48,107-341,358-457) in the reference's f32 arithmetic.  Tables are f32
@@ -644,6 +662,12 @@ int mi355_dense_set_gptq(void* model, int32_t layer, int32_t which, const void* 
  * shards as given (scale rows are not re-sliced). */
 int mi355_dense_set_fp8(void* model, int32_t layer, int32_t which, const void* w_host, const float* scale_host,
                         int32_t n, int32_t k);
+/* MXFP4 projection (`LnMxfp4`, linear.rs:1677-1757) instead of a dense one: blocks [n, k/2] bytes and e8m0 scales [n, k/32] from the
+ * HOST in checkpoint order (see mi355_mxfp4_linear_tiled); slots MI355_W_WQ .. MI355_W_W3 (gate and up are packed along n: the scales
+ * are per row, so intermediate % 16 == 0 suffices).  n % 16 == 0, k % 128 == 0; refused after mi355_dense_finalize and on a slot that
+ * holds another format.  Under tensor parallelism the tensors are this rank's shards as given. */
+int mi355_dense_set_mxfp4(void* model, int32_t layer, int32_t which, const void* blocks_host, const void* scales_host,
+                          int32_t n, int32_t k);
 /* tensor parallel (distributed.rs:243-249,492-534,696-711,1632-1667): comm from mi355_comm_create (borrowed);
  * all-reduce of the 16-bit stream after o_proj / down_proj, vocab-parallel lm_head + all-gather */
 int mi355_dense_set_comm(void* model, void* comm);
