@@ -131,6 +131,8 @@ _sig("mi355_fp8_tile_repack", ctypes.c_int, [c_vp, c_vp, c_i32, c_i32, c_i64])
 _sig("mi355_fp8_linear_tiled", ctypes.c_int, [c_vp] * 6 + [c_i32] * 7 + [c_i64])
 _sig("mi355_mxfp4_tile_repack", ctypes.c_int, [c_vp] * 4 + [c_i32, c_i32, c_i64])
 _sig("mi355_mxfp4_linear_tiled", ctypes.c_int, [c_vp] * 6 + [c_i32] * 6 + [c_i64])
+_sig("mi355_nvfp4_tile_repack", ctypes.c_int, [c_vp] * 4 + [c_i32, c_i32, c_i64])
+_sig("mi355_nvfp4_linear_tiled", ctypes.c_int, [c_vp] * 6 + [c_i32] * 4 + [c_f32] * 2 + [c_i32, c_i32, c_i64])
 
 
 class LlamaConfig(ctypes.Structure):
@@ -249,6 +251,7 @@ _sig("mi355_dense_set_weight_dev", ctypes.c_int, [c_vp, c_i32, c_i32, c_vp, c_i6
 _sig("mi355_dense_set_gptq", ctypes.c_int, [c_vp, c_i32, c_i32, c_vp, c_vp, c_i32, c_i32, c_i32])
 _sig("mi355_dense_set_fp8", ctypes.c_int, [c_vp, c_i32, c_i32, c_vp, c_vp, c_i32, c_i32])
 _sig("mi355_dense_set_mxfp4", ctypes.c_int, [c_vp, c_i32, c_i32, c_vp, c_vp, c_i32, c_i32])
+_sig("mi355_dense_set_nvfp4", ctypes.c_int, [c_vp, c_i32, c_i32, c_vp, c_vp, c_f32, c_i32, c_i32])
 _sig("mi355_dense_set_comm", ctypes.c_int, [c_vp, c_vp])
 _sig("mi355_dense_set_rope_tables", ctypes.c_int, [c_vp, c_vp, c_vp, c_i32])
 _sig("mi355_llama_set_rope_tables", ctypes.c_int, [c_vp, c_vp, c_vp, c_i32])

@@ -63,12 +63,16 @@ struct FLin { uint8_t* w = nullptr; float* scale = nullptr; };
 // MXFP4 variant (`LnMxfp4`, linear.rs:1677-1757): e2m1 nibbles and e8m0 group-32 scales re-ordered at load time into the two planes of
 // mi355_mxfp4_tile_repack (16-row x 128-k tiles); gate and up concatenated along N (the scales are per row: tiles simply follow each other)
 struct MLin { uint8_t* w = nullptr; uint8_t* scale = nullptr; };
+// NVFP4 variant (`LnNvfp4`, linear.rs:1760-1943): e2m1 nibbles and e4m3 group-16 scales in the two planes of mi355_nvfp4_tile_repack plus
+// the per-tensor f32 multiplier; gate and up concatenated along N, each with its own multiplier (g: gate or the only tensor, g_up: up)
+struct NLin { uint8_t* w = nullptr; uint8_t* scale = nullptr; float g = 1.f, g_up = 1.f; };
 
 struct DLayer {
     uint16_t *wq = nullptr, *wk = nullptr, *wv = nullptr, *wo = nullptr, *gate_up = nullptr, *w2 = nullptr;
     QLin gq[7];                // indexed by MI355_W_WQ .. MI355_W_W3 (W1 holds the packed gate_up, W3 unused)
     FLin fq[7];                // the same slots in FP8
     MLin mq[7];                // ... and in MXFP4
+    NLin nq[7];                // ... and in NVFP4
     uint16_t *bq = nullptr, *bk = nullptr, *bv = nullptr;
     uint16_t *attn_norm = nullptr, *ffn_norm = nullptr, *attn_norm_b = nullptr, *ffn_norm_b = nullptr;
 };
@@ -190,13 +194,15 @@ int norm(const DModel* m, uint16_t* out, const uint16_t* x, const uint16_t* w, c
     return mi355_rms_norm(out, x, w, T, c.hidden, c.rms_eps, c.dtype, c.dtype, stream);
 }
 
-// Linear::forward, the QLinear GPTQ arm, LnFp8 or LnMxfp4 (linear.rs:124-172 / 854-906 / 918-1221 / 1677-1757), same fused epilogues
-int linear(const DModel* m, const uint16_t* w, const QLin& g, const FLin& f, const MLin& x4, void* out, const void* x, const void* bias, const void* resid,
+// Linear::forward, the QLinear GPTQ arm, LnFp8, LnMxfp4 or LnNvfp4 (linear.rs:124-172 / 854-906 / 918-1221 / 1677-1757 / 1760-1943), same
+// fused epilogues
+int linear(const DModel* m, const uint16_t* w, const QLin& g, const FLin& f, const MLin& x4, const NLin& n4, void* out, const void* x, const void* bias, const void* resid,
            int T, int n, int k, int epi, int64_t stream) {
     if (g.qw)
         return mi355_gptq_linear_tiled(out, x, g.qw, g.scales, nullptr, MI355_ZERO_SYM8, 0, bias, resid, T, n, k, g.group, m->cfg.dtype, epi, stream);
     if (f.w) return mi355_fp8_linear_tiled(out, x, f.w, f.scale, bias, resid, T, n, k, 128, 128, m->cfg.dtype, epi, stream);
     if (x4.w) return mi355_mxfp4_linear_tiled(out, x, x4.w, x4.scale, bias, resid, T, n, k, 32, m->cfg.dtype, epi, stream);
+    if (n4.w) return mi355_nvfp4_linear_tiled(out, x, n4.w, n4.scale, bias, resid, T, n, k, 16, n4.g, n4.g_up, m->cfg.dtype, epi, stream);
     if (!w) return (int)hipErrorInvalidValue;
     if (m->tiled.count(w)) return mi355_linear_tiled(out, x, w, bias, resid, T, n, k, m->cfg.dtype, epi, stream);
     return mi355_linear(out, x, w, bias, resid, T, n, k, m->cfg.dtype, epi, stream);
@@ -236,7 +242,7 @@ int finalize_weights(DModel* m) {
 
 // xs += x . w^T (the residual epilogue of o_proj / down_proj).  With 4-bit weights and 1..4 tokens the launch also leaves the sums
 // of squares of the new xs rows in m->ss (*ss_valid), so the consumer's RmsNorm needs no launch of its own.
-int resid_linear(const DModel* m, const uint16_t* w, const QLin& g, const FLin& f, const MLin& x4, const void* x, int T, int n, int k, bool* ss_valid, int64_t stream) {
+int resid_linear(const DModel* m, const uint16_t* w, const QLin& g, const FLin& f, const MLin& x4, const NLin& n4, const void* x, int T, int n, int k, bool* ss_valid, int64_t stream) {
     *ss_valid = false;
     if (g.qw && T <= 4 && m->cfg.norm_type == 0) {
         const int rc = mi355_internal_gptq_small_linear(m->xs, x, g.qw, g.scales, nullptr, m->xs, nullptr, 0.f, nullptr, m->ss, T, n, k,
@@ -244,7 +250,7 @@ int resid_linear(const DModel* m, const uint16_t* w, const QLin& g, const FLin& 
         if (rc == 0) { *ss_valid = true; return 0; }
         if (rc != -4) return rc;
     }
-    return linear(m, w, g, f, x4, m->xs, x, nullptr, m->xs, T, n, k, MI355_EPI_RESID, stream);
+    return linear(m, w, g, f, x4, n4, m->xs, x, nullptr, m->xs, T, n, k, MI355_EPI_RESID, stream);
 }
 
 int choose_partition(int batch, int kv_heads, int ctx_cap) {
@@ -299,6 +305,7 @@ void mi355_dense_destroy(void* mp) {
         for (auto& g : L.gq) { if (g.qw) (void)hipFree(g.qw); if (g.scales) (void)hipFree(g.scales); }
         for (auto& f : L.fq) { if (f.w) (void)hipFree(f.w); if (f.scale) (void)hipFree(f.scale); }
         for (auto& x4 : L.mq) { if (x4.w) (void)hipFree(x4.w); if (x4.scale) (void)hipFree(x4.scale); }
+        for (auto& n4 : L.nq) { if (n4.w) (void)hipFree(n4.w); if (n4.scale) (void)hipFree(n4.scale); }
     }
     for (auto& kv : m->graphs) {
         if (kv.second.exec) (void)hipGraphExecDestroy(kv.second.exec);
@@ -358,10 +365,10 @@ static int dense_set_weight_impl(void* mp, int32_t layer, int32_t which, const v
     }
     if (n_elems != expect) return (int)hipErrorInvalidValue;
     if (m->finalized) return (int)hipErrorInvalidValue;      // mi355_dense_finalize / the first step froze the weights: every slot alike
-    // one format per projection slot: a slot that mi355_dense_set_fp8 / mi355_dense_set_mxfp4 filled takes no 16-bit weight
+    // one format per projection slot: a slot that mi355_dense_set_fp8 / _mxfp4 / _nvfp4 filled takes no 16-bit weight
     if (layer >= 0 && which >= MI355_W_WQ && which <= MI355_W_W3) {
         const int s = which == MI355_W_W3 ? MI355_W_W1 : which;
-        if (m->layers[layer].fq[s].w || m->layers[layer].mq[s].w) return (int)hipErrorInvalidValue;
+        if (m->layers[layer].fq[s].w || m->layers[layer].mq[s].w || m->layers[layer].nq[s].w) return (int)hipErrorInvalidValue;
     }
     if (total == 0) total = expect;
     if (!*slot) DHIP(hipMalloc((void**)slot, (size_t)total * 2));
@@ -383,8 +390,8 @@ int mi355_dense_set_gptq(void* mp, int32_t layer, int32_t which, const void* qwe
     QLin& q = m->layers[layer].gq[gu ? MI355_W_W1 : which];
     const int ntot = gu ? 2 * I : n, col0 = which == MI355_W_W3 ? I : 0;
     if (gu && n != I) return (int)hipErrorInvalidValue;
-    if (m->layers[layer].fq[gu ? MI355_W_W1 : which].w || m->layers[layer].mq[gu ? MI355_W_W1 : which].w)
-        return (int)hipErrorInvalidValue;                                                      // the slot holds an FP8 / MXFP4 projection
+    if (m->layers[layer].fq[gu ? MI355_W_W1 : which].w || m->layers[layer].mq[gu ? MI355_W_W1 : which].w || m->layers[layer].nq[gu ? MI355_W_W1 : which].w)
+        return (int)hipErrorInvalidValue;                                                      // the slot holds an FP8 / MXFP4 / NVFP4 projection
     if (q.group && q.group != g) return (int)hipErrorInvalidValue;
     q.group = g;
     if (!q.qw) DHIP(hipMalloc((void**)&q.qw, (size_t)(k / 8) * ntot * 4));
@@ -416,7 +423,7 @@ int mi355_dense_set_fp8(void* mp, int32_t layer, int32_t which, const void* w_ho
     const int slot = gu ? MI355_W_W1 : which;
     const int exp_n[7] = {HD, KD, KD, hid, I, hid, I}, exp_k[7] = {hid, hid, hid, HD, hid, I, hid};
     const uint16_t* const dense[7] = {L.wq, L.wk, L.wv, L.wo, L.gate_up, L.w2, L.gate_up};
-    if (n != exp_n[which] || k != exp_k[which] || dense[which] || L.gq[slot].qw || L.mq[slot].w) return (int)hipErrorInvalidValue;
+    if (n != exp_n[which] || k != exp_k[which] || dense[which] || L.gq[slot].qw || L.mq[slot].w || L.nq[slot].w) return (int)hipErrorInvalidValue;
     FLin& f = L.fq[slot];
     const int ntot = gu ? 2 * I : n, row0 = which == MI355_W_W3 ? I : 0, nkb = k / 128;
     // checkpoint layout -> staging buffer -> tiles [row0 / 16, (row0 + n) / 16) of the tiled image (a tile's k-blocks are contiguous)
@@ -451,7 +458,7 @@ int mi355_dense_set_mxfp4(void* mp, int32_t layer, int32_t which, const void* bl
     const int slot = gu ? MI355_W_W1 : which;
     const int exp_n[7] = {HD, KD, KD, hid, I, hid, I}, exp_k[7] = {hid, hid, hid, HD, hid, I, hid};
     const uint16_t* const dense[7] = {L.wq, L.wk, L.wv, L.wo, L.gate_up, L.w2, L.gate_up};
-    if (n != exp_n[which] || k != exp_k[which] || dense[which] || L.gq[slot].qw || L.fq[slot].w) return (int)hipErrorInvalidValue;
+    if (n != exp_n[which] || k != exp_k[which] || dense[which] || L.gq[slot].qw || L.fq[slot].w || L.nq[slot].w) return (int)hipErrorInvalidValue;
     MLin& x4 = L.mq[slot];
     const int ntot = gu ? 2 * I : n, row0 = which == MI355_W_W3 ? I : 0;
     const size_t wb = (size_t)n * (k / 2), sb = (size_t)n * (k / 32);               // bytes of this tensor's two planes
@@ -471,6 +478,46 @@ int mi355_dense_set_mxfp4(void* mp, int32_t layer, int32_t which, const void* bl
         x4 = MLin{};
     }
     return rc;
+}
+
+/* NVFP4 projection from HOST checkpoint tensors (`LnNvfp4`, linear.rs:1760-1943): blocks [n, k/2] bytes, e4m3fn scales [n, k/16], and the
+ * f32 multiplier the reference ends up with (linear.rs:1829-1853).  gate_proj (W1) and up_proj (W3) are concatenated along n -- the up
+ * tiles follow the gate tiles in both planes (intermediate % 16 == 0) -- and arrive in separate calls, each with its own multiplier: the
+ * slot keeps both and the silu*up epilogue stays fused. */
+int mi355_dense_set_nvfp4(void* mp, int32_t layer, int32_t which, const void* blocks_host, const void* scales_host, float global_scale,
+                          int32_t n, int32_t k) {
+    DModel* m = static_cast<DModel*>(mp);
+    if (!m || layer < 0 || layer >= m->cfg.n_layers || !blocks_host || !scales_host || m->finalized) return (int)hipErrorInvalidValue;
+    if (which < MI355_W_WQ || which > MI355_W_W3 || n <= 0 || k <= 0 || (k % 128) || (n % 16)) return (int)hipErrorInvalidValue;
+    const mi355_dense_config& c = m->cfg;
+    const int hid = c.hidden, HD = c.n_heads * c.head_dim, KD = c.n_kv_heads * c.head_dim, I = c.intermediate;
+    DLayer& L = m->layers[layer];
+    const bool gu = which == MI355_W_W1 || which == MI355_W_W3;
+    const int slot = gu ? MI355_W_W1 : which;
+    const int exp_n[7] = {HD, KD, KD, hid, I, hid, I}, exp_k[7] = {hid, hid, hid, HD, hid, I, hid};
+    const uint16_t* const dense[7] = {L.wq, L.wk, L.wv, L.wo, L.gate_up, L.w2, L.gate_up};
+    if (n != exp_n[which] || k != exp_k[which] || dense[which] || L.gq[slot].qw || L.fq[slot].w || L.mq[slot].w) return (int)hipErrorInvalidValue;
+    NLin& n4 = L.nq[slot];
+    const int ntot = gu ? 2 * I : n, row0 = which == MI355_W_W3 ? I : 0;
+    const size_t wb = (size_t)n * (k / 2), sb = (size_t)n * (k / 16);               // bytes of this tensor's two planes
+    // checkpoint layout -> staging buffer (blocks, then scales: wb is a multiple of 8) -> tiles [row0 / 16, (row0 + n) / 16) of both planes
+    uint8_t* stage = nullptr;
+    int rc = n4.w ? 0 : (int)hipMalloc((void**)&n4.w, (size_t)ntot * (k / 2));
+    if (!rc && !n4.scale) rc = (int)hipMalloc((void**)&n4.scale, (size_t)ntot * (k / 16));
+    if (!rc) rc = (int)hipMalloc((void**)&stage, wb + sb);
+    if (!rc) rc = (int)hipMemcpy(stage, blocks_host, wb, hipMemcpyHostToDevice);
+    if (!rc) rc = (int)hipMemcpy(stage + wb, scales_host, sb, hipMemcpyHostToDevice);
+    if (!rc) rc = mi355_nvfp4_tile_repack(stage, stage + wb, n4.w + (size_t)row0 * (k / 2), n4.scale + (size_t)row0 * (k / 16), n, k, 0);
+    if (!rc) rc = (int)hipDeviceSynchronize();
+    if (stage) (void)hipFree(stage);
+    if (rc) {   // a half-filled slot must not look populated (it would switch the layer to the unfused path and multiply garbage)
+        if (n4.w) (void)hipFree(n4.w);
+        if (n4.scale) (void)hipFree(n4.scale);
+        n4 = NLin{};
+        return rc;
+    }
+    (which == MI355_W_W3 ? n4.g_up : n4.g) = global_scale;
+    return 0;
 }
 
 int mi355_dense_set_rope_tables(void* mp, const float* cos_host, const float* sin_host, int32_t n_positions) {
@@ -568,10 +615,10 @@ int mi355_dense_forward(void* mp, const uint32_t* tokens, const int64_t* positio
         // and 1..4 tokens that launch also applies the RmsNorm while it stages the activations (no norm launch)
         int rc3 = -4;
         bool normed = false, roped = false;
-        // an FP8 or MXFP4 projection among q, k, v: norm, three launches, mi355_rope_inplace, mi355_reshape_and_cache (nothing fused: the
+        // an FP8, MXFP4 or NVFP4 projection among q, k, v: norm, three launches, mi355_rope_inplace, mi355_reshape_and_cache (nothing fused: the
         // q|k|v launch below would see a null 16-bit weight)
         bool any_f = false;
-        for (const int s : {MI355_W_WQ, MI355_W_WK, MI355_W_WV}) any_f = any_f || L.fq[s].w || L.mq[s].w;
+        for (const int s : {MI355_W_WQ, MI355_W_WK, MI355_W_WV}) any_f = any_f || L.fq[s].w || L.mq[s].w || L.nq[s].w;
         if (!any_f) {
             const QLin &gq = L.gq[MI355_W_WQ], &gk = L.gq[MI355_W_WK], &gv = L.gq[MI355_W_WV];
             const bool all_q = gq.qw && gk.qw && gv.qw && gq.group == gk.group && gq.group == gv.group;
@@ -610,9 +657,9 @@ int mi355_dense_forward(void* mp, const uint32_t* tokens, const int64_t* positio
         }
         if (rc3 != 0 && !normed) DCHECK(norm(m, m->xn, m->xs, L.attn_norm, L.attn_norm_b, T, stream));
         if (rc3 != 0) {
-        DCHECK(linear(m, L.wq, L.gq[MI355_W_WQ], L.fq[MI355_W_WQ], L.mq[MI355_W_WQ], m->q, m->xn, L.bq, nullptr, T, H * D, hid, MI355_EPI_STORE, stream));
-        DCHECK(linear(m, L.wk, L.gq[MI355_W_WK], L.fq[MI355_W_WK], L.mq[MI355_W_WK], m->k, m->xn, L.bk, nullptr, T, Hkv * D, hid, MI355_EPI_STORE, stream));
-        DCHECK(linear(m, L.wv, L.gq[MI355_W_WV], L.fq[MI355_W_WV], L.mq[MI355_W_WV], m->v, m->xn, L.bv, nullptr, T, Hkv * D, hid, MI355_EPI_STORE, stream));
+        DCHECK(linear(m, L.wq, L.gq[MI355_W_WQ], L.fq[MI355_W_WQ], L.mq[MI355_W_WQ], L.nq[MI355_W_WQ], m->q, m->xn, L.bq, nullptr, T, H * D, hid, MI355_EPI_STORE, stream));
+        DCHECK(linear(m, L.wk, L.gq[MI355_W_WK], L.fq[MI355_W_WK], L.mq[MI355_W_WK], L.nq[MI355_W_WK], m->k, m->xn, L.bk, nullptr, T, Hkv * D, hid, MI355_EPI_STORE, stream));
+        DCHECK(linear(m, L.wv, L.gq[MI355_W_WV], L.fq[MI355_W_WV], L.mq[MI355_W_WV], L.nq[MI355_W_WV], m->v, m->xn, L.bv, nullptr, T, Hkv * D, hid, MI355_EPI_STORE, stream));
         }
         // q,k -> f32 -> rope -> model dtype                                  attention.rs:644-690
         // (decode steps without an fp8 cache: RoPE and the cache write share one launch)
@@ -672,11 +719,11 @@ int mi355_dense_forward(void* mp, const uint32_t* tokens, const int64_t* positio
         const bool tp = m->comm != nullptr;
         const int add_grid = (int)std::min<int64_t>(((int64_t)T * hid + 255) / 256, 2048);
         if (tp) {
-            DCHECK(linear(m, L.wo, L.gq[MI355_W_WO], L.fq[MI355_W_WO], L.mq[MI355_W_WO], m->xn, m->attn, nullptr, nullptr, T, hid, H * D, MI355_EPI_STORE, stream));
+            DCHECK(linear(m, L.wo, L.gq[MI355_W_WO], L.fq[MI355_W_WO], L.mq[MI355_W_WO], L.nq[MI355_W_WO], m->xn, m->attn, nullptr, nullptr, T, hid, H * D, MI355_EPI_STORE, stream));
             DCHECK(mi355_comm_all_reduce(m->comm, m->xn, (int64_t)T * hid, dt, stream));
             hipLaunchKernelGGL(add16_kernel, dim3(add_grid), dim3(256), 0, st, m->xs, m->xn, (int64_t)T * hid, dt == MI355_DTYPE_BF16);
         } else {
-            DCHECK(resid_linear(m, L.wo, L.gq[MI355_W_WO], L.fq[MI355_W_WO], L.mq[MI355_W_WO], m->attn, T, hid, H * D, &ss_valid, stream));
+            DCHECK(resid_linear(m, L.wo, L.gq[MI355_W_WO], L.fq[MI355_W_WO], L.mq[MI355_W_WO], L.nq[MI355_W_WO], m->attn, T, hid, H * D, &ss_valid, stream));
         }
         // xs = down(silu(gate) * up) + residual                              llama.rs:59-61, mlp.rs:440-458
         int rc_gu = -4;
@@ -688,14 +735,14 @@ int mi355_dense_forward(void* mp, const uint32_t* tokens, const int64_t* positio
         }
         if (rc_gu != 0) {
         DCHECK(norm(m, m->xn, m->xs, L.ffn_norm, L.ffn_norm_b, T, stream));
-        DCHECK(linear(m, L.gate_up, L.gq[MI355_W_W1], L.fq[MI355_W_W1], L.mq[MI355_W_W1], m->h, m->xn, nullptr, nullptr, T, 2 * I, hid, MI355_EPI_SILU_MUL, stream));
+        DCHECK(linear(m, L.gate_up, L.gq[MI355_W_W1], L.fq[MI355_W_W1], L.mq[MI355_W_W1], L.nq[MI355_W_W1], m->h, m->xn, nullptr, nullptr, T, 2 * I, hid, MI355_EPI_SILU_MUL, stream));
         }
         if (tp) {
-            DCHECK(linear(m, L.w2, L.gq[MI355_W_W2], L.fq[MI355_W_W2], L.mq[MI355_W_W2], m->xn, m->h, nullptr, nullptr, T, hid, I, MI355_EPI_STORE, stream));
+            DCHECK(linear(m, L.w2, L.gq[MI355_W_W2], L.fq[MI355_W_W2], L.mq[MI355_W_W2], L.nq[MI355_W_W2], m->xn, m->h, nullptr, nullptr, T, hid, I, MI355_EPI_STORE, stream));
             DCHECK(mi355_comm_all_reduce(m->comm, m->xn, (int64_t)T * hid, dt, stream));
             hipLaunchKernelGGL(add16_kernel, dim3(add_grid), dim3(256), 0, st, m->xs, m->xn, (int64_t)T * hid, dt == MI355_DTYPE_BF16);
         } else {
-            DCHECK(resid_linear(m, L.w2, L.gq[MI355_W_W2], L.fq[MI355_W_W2], L.mq[MI355_W_W2], m->h, T, hid, I, &ss_valid, stream));
+            DCHECK(resid_linear(m, L.w2, L.gq[MI355_W_W2], L.fq[MI355_W_W2], L.mq[MI355_W_W2], L.nq[MI355_W_W2], m->h, T, hid, I, &ss_valid, stream));
         }
     }
     if (window) {                                                           // the residual stream after the window's last layer
@@ -711,14 +758,14 @@ int mi355_dense_forward(void* mp, const uint32_t* tokens, const int64_t* positio
     DCHECK(norm(m, m->xn, last, m->output_norm, m->output_norm_b, num_seqs, stream));
     if (m->comm) {                                                          // VocabParallelLinear (distributed.rs:1632-1667)
         const int W = c.tp_world > 1 ? c.tp_world : 1;
-        DCHECK(linear(m, m->output, QLin{}, FLin{}, MLin{}, m->lg16, m->xn, nullptr, nullptr, num_seqs, c.vocab, hid, MI355_EPI_STORE, stream));
+        DCHECK(linear(m, m->output, QLin{}, FLin{}, MLin{}, NLin{}, m->lg16, m->xn, nullptr, nullptr, num_seqs, c.vocab, hid, MI355_EPI_STORE, stream));
         DCHECK(mi355_comm_all_gather(m->comm, m->lg16, m->lg_gather, (int64_t)num_seqs * c.vocab, dt, stream));
         // narrowed to the real vocabulary as VocabParallelLinear::forward does before sampling (the greedy loop sampled
         // over the padded row, where a zero row beats an all-negative row and the token id leaves the embedding table)
         hipLaunchKernelGGL(gather_transpose16_kernel, dim3(512), dim3(256), 0, st, m->lg16, m->lg_gather, W, num_seqs, c.vocab, logits_width(c));
         return mi355_cast(logits, m->lg16, (int64_t)num_seqs * logits_width(c), dt, MI355_DTYPE_F32, stream);
     }
-    DCHECK(linear(m, m->output, QLin{}, FLin{}, MLin{}, m->lg16, m->xn, nullptr, nullptr, num_seqs, c.vocab, hid, MI355_EPI_STORE, stream));
+    DCHECK(linear(m, m->output, QLin{}, FLin{}, MLin{}, NLin{}, m->lg16, m->xn, nullptr, nullptr, num_seqs, c.vocab, hid, MI355_EPI_STORE, stream));
     return mi355_cast(logits, m->lg16, (int64_t)num_seqs * c.vocab, dt, MI355_DTYPE_F32, stream);
 }
 

@@ -116,6 +116,17 @@ class DenseLlama:
             raise ValueError(f"set_mxfp4 {name}: scale shape {sc.shape} does not match [{n}, {k}] weights in groups of 32")
         _check(lib.mi355_dense_set_mxfp4(self.h, layer, W_SLOTS[name], b.ctypes.data, sc.ctypes.data, n, k), f"set_mxfp4 {name}")
 
+    def set_nvfp4(self, layer, name, blocks_u8, scales_u8, global_scale=1.0):
+        """`LnNvfp4` projection (linear.rs:1760-1943): blocks [n, k/2] uint8 (two e2m1 codes per byte, low nibble first), scales
+        [n, k/16] uint8 e4m3fn, global_scale the f32 multiplier (1 / weight_global_scale, or weight_scale_2)"""
+        b = np.ascontiguousarray(blocks_u8, np.uint8)
+        sc = np.ascontiguousarray(scales_u8, np.uint8)
+        n, k = b.shape[0], b.shape[1] * 2
+        if sc.shape != (n, k // 16) or k % 16:
+            raise ValueError(f"set_nvfp4 {name}: scale shape {sc.shape} does not match [{n}, {k}] weights in groups of 16")
+        _check(lib.mi355_dense_set_nvfp4(self.h, layer, W_SLOTS[name], b.ctypes.data, sc.ctypes.data, float(global_scale), n, k),
+               f"set_nvfp4 {name}")
+
     def load_oracle_weights(self, W):
         for name in ("tok_embd", "output_norm", "output", "output_norm_b"):
             if name in W:

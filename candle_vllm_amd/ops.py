@@ -682,6 +682,40 @@ class Mxfp4Linear:
         return out
 
 
+class Nvfp4Linear:
+    """`LnNvfp4` (linear.rs:1760-1943): blocks [out, in/2] uint8 (two e2m1 codes per byte, low nibble first) + e4m3fn scales
+    [out, in/16] uint8 + the f32 multiplier the reference ends up with (1 / weight_global_scale, or weight_scale_2, or 1.0); re-ordered
+    into the tile image at construction (out % 16 == 0, in % 128 == 0).  W4A16: 16-bit activations, exact weights, f32 accumulation;
+    the decode epilogues fused as in `Linear`.  `global_scale_up` is the multiplier of the up half of a packed [gate; up] matrix
+    (SILU_MUL; default: the same as the gate's)."""
+
+    def __init__(self, blocks_u8, scales_u8, global_scale=1.0, bias=None, global_scale_up=None):
+        if blocks_u8.dtype != torch.uint8 or scales_u8.dtype != torch.uint8:
+            raise RuntimeError("Nvfp4Linear takes uint8 e2m1 blocks and uint8 e4m3fn scales")
+        self.n, self.k = blocks_u8.shape[0], blocks_u8.shape[1] * 2
+        if tuple(scales_u8.shape) != (self.n, self.k // 16) or self.k % 16:
+            raise RuntimeError("scales must be [out, in / 16]")
+        self.bias = bias
+        self.global_scale = float(global_scale)
+        self.global_scale_up = self.global_scale if global_scale_up is None else float(global_scale_up)
+        blocks_u8, scales_u8 = blocks_u8.contiguous(), scales_u8.contiguous()   # the repack reads row-major through the raw pointers
+        self.weight, self.scale = torch.empty_like(blocks_u8), torch.empty_like(scales_u8)
+        _check(lib.mi355_nvfp4_tile_repack(_dev(blocks_u8), _dev(scales_u8), _dev(self.weight), _dev(self.scale), self.n, self.k,
+                                           _stream()), "nvfp4_tile_repack")
+
+    def forward(self, x, *, epilogue=EPI_STORE, residual=None, out=None):
+        x2 = x.reshape(-1, self.k)
+        T = x2.shape[0]
+        n_out = self.n // 2 if epilogue == EPI_SILU_MUL else self.n
+        if out is None:
+            out = torch.empty((T, n_out), dtype=x.dtype, device=x.device)
+        _check(lib.mi355_nvfp4_linear_tiled(_dev(out), _dev(x2), _dev(self.weight), _dev(self.scale),
+                                            _dev(self.bias) if self.bias is not None else None,
+                                            _dev(residual) if residual is not None else None, T, self.n, self.k,
+                                            16, self.global_scale, self.global_scale_up, _DT[x.dtype], epilogue, _stream()), "nvfp4_linear")
+        return out
+
+
 def rope_tables(rope_theta, rotary_dim, max_seq_len, scaling=None, max_position_embeddings=0):
     """`ScalingRotaryEmbedding::new` (layers/rotary_emb.rs:107-341): cos, sin f32 [n, rotary_dim/2] built by the
     library's host code.  scaling: None or a `_lib.RopeScaling`."""

@@ -456,6 +456,30 @@ int mi355_mxfp4_tile_repack(const void* in_blocks, const void* in_scales, void* 
 int mi355_mxfp4_linear_tiled(void* out, const void* x, const void* w_tiled, const void* s_tiled,
                              const void* bias, const void* residual, int32_t num_tokens, int32_t n, int32_t k,
                              int32_t group, int32_t dtype, int32_t epilogue, int64_t stream);
+/* `LnNvfp4::forward` (linear.rs:1760-1943; selected at :1375-1397, :1526-1554): NVFP4 checkpoints (`quant_method: "nvfp4"`, ModelOpt /
+ * compressed-tensors exports).  blocks is [n, k/2] bytes in MXFP4's coding (element 2j in the LOW nibble of byte j), scales is [n, k/16]
+ * e4m3fn bytes, one per 16 k, and global_scale is the f32 MULTIPLIER the reference ends up with (1 / weight_global_scale, or
+ * weight_scale_2, or 1.0: linear.rs:1829-1853):
+ *   out = global_scale * (x . (e2m1(blocks) * e4m3(scales))^T) (+bias), x / out / bias / residual in `dtype` (BF16 / F16).
+ * W4A16: e2m1 * e4m3 is an exact 16-bit number in both dtypes, the activations are not quantised (`input_scale`, linear.rs:1855-1879, is
+ * an activation-quantisation scale and is ignored), accumulation is f32 through all of K, and global_scale multiplies the f32 sum before
+ * the first rounding; epilogues and rounding points as mi355_linear with global_scale * sum in the place of the sum (SILU_MUL: the image
+ * is that of the packed [gate; up] matrix, n % 32 == 0, the gate half takes global_scale and the up half global_scale_up; otherwise
+ * global_scale_up is not read).  Scale codes 0x00..0x7E decode exactly, zero and the subnormals included; 0x7F / 0xFF (NaN) makes the
+ * outputs of its row NaN; other codes with the sign bit set run clean with no promise on the value.  Served: n % 16 == 0,
+ * k % 128 == 0, group == 16; anything else returns hipErrorNotSupported / hipErrorInvalidValue before any launch.  The MLX u32 packing
+ * and swizzled scale tensors are not read.
+ * mi355_nvfp4_tile_repack (linear.rs:1760-1943, load time): checkpoint tensors -> the two planes the kernels stream, device to device,
+ * in != out, in_scales 8-byte aligned.  Block byte (n, j) goes where mi355_mxfp4_tile_repack puts it:
+ *   (((n/16) * (k_total/128) + k/128) * 64 + 16 * ((k%32)/8) + n%16) * 16 + 4 * ((k%128)/32) + (k%8)/2        of out_tiles (n * k/2 bytes)
+ * and scale byte (n, g = k/16) to byte
+ *   ((((n/16) * (k_total/128) + g/8) * 2 + g%2) * 16 + n%16) * 4 + (g%8)/2                                    of out_scales (n * k/16 bytes)
+ * -- 128 B per 16-row tile and 128-k block; the four scales an MFMA B-fragment lane needs in a k-block are one dword. */
+int mi355_nvfp4_tile_repack(const void* in_blocks, const void* in_scales, void* out_tiles, void* out_scales,
+                            int32_t n, int32_t k, int64_t stream);
+int mi355_nvfp4_linear_tiled(void* out, const void* x, const void* w_tiled, const void* s_tiled, const void* bias,
+                             const void* residual, int32_t num_tokens, int32_t n, int32_t k, int32_t group,
+                             float global_scale, float global_scale_up, int32_t dtype, int32_t epilogue, int64_t stream);
 
 /* RoPE cos/sin table builders (HOST): DefaultRotaryEmbedding::new / ScalingRotaryEmbedding::new
  * (layers/rotary_emb.rs:14-48,107-341,358-457) in the reference's f32 arithmetic.  Tables are f32
@@ -668,6 +692,12 @@ int mi355_dense_set_fp8(void* model, int32_t layer, int32_t which, const void* w
  * holds another format.  Under tensor parallelism the tensors are this rank's shards as given. */
 int mi355_dense_set_mxfp4(void* model, int32_t layer, int32_t which, const void* blocks_host, const void* scales_host,
                           int32_t n, int32_t k);
+/* NVFP4 projection (`LnNvfp4`, linear.rs:1760-1943) instead of a dense one: blocks [n, k/2] bytes and e4m3fn scales [n, k/16] from the
+ * HOST in checkpoint order, global_scale the f32 multiplier (see mi355_nvfp4_linear_tiled); slots MI355_W_WQ .. MI355_W_W3 (gate and up
+ * are packed along n and each keeps its own global_scale).  n % 16 == 0, k % 128 == 0; refused after mi355_dense_finalize and on a slot
+ * that holds another format.  Under tensor parallelism the tensors are this rank's shards as given. */
+int mi355_dense_set_nvfp4(void* model, int32_t layer, int32_t which, const void* blocks_host, const void* scales_host,
+                          float global_scale, int32_t n, int32_t k);
 /* tensor parallel (distributed.rs:243-249,492-534,696-711,1632-1667): comm from mi355_comm_create (borrowed);
  * all-reduce of the 16-bit stream after o_proj / down_proj, vocab-parallel lm_head + all-gather */
 int mi355_dense_set_comm(void* model, void* comm);
