@@ -14,6 +14,7 @@ enum {
     MI355_SCR_COMM = 9,          // one-shot all-reduce staging
     MI355_SCR_GPTQ_WIDE = 10,    // 5..64-token launches of tiled 4-bit weights: split-K partial sums (gptq_wide.inc)
     MI355_SCR_PF_FP8 = 11,       // prompt attention over an e4m3 cache: the sequences' blocks as bf16 + their block table (prefill_attention.hip)
+    MI355_SCR_MX4MOE_PLAN = 12,  // MXFP4 MoE experts: run count, runs and row list of one launch (mxfp4_moe.hip; rewritten by every call)
 };
 
 // *out = a device buffer of >= bytes owned by (current device, st, key).  zero_on_create: the buffer is cleared (on `st`)

@@ -682,6 +682,54 @@ class Mxfp4Linear:
         return out
 
 
+class Mxfp4MoE:
+    """`FusedMoeMxfp4` (layers/moe.rs:1484-1836): the experts' packed gate|up blocks [E, 2I, H/2] and down blocks [E, H, I/2] (uint8, two
+    e2m1 codes per byte) with their e8m0 scales [E, 2I, H/32] / [E, H, I/32]; re-ordered into the experts' tile images at construction.
+    `gemm` is one `moe_gemm_mxfp4` call (routing on the device, no host round trip), `forward` is `forward_with_routing`."""
+
+    def __init__(self, gate_up_blocks, gate_up_scales, down_blocks, down_scales):
+        self.w = {}
+        for which, b, s in (("gate_up", gate_up_blocks, gate_up_scales), ("down", down_blocks, down_scales)):
+            if b.dtype != torch.uint8 or s.dtype != torch.uint8 or b.dim() != 3:
+                raise RuntimeError("Mxfp4MoE takes uint8 e2m1 blocks [E, out, in / 2] and uint8 e8m0 scales [E, out, in / 32]")
+            E, n, k = b.shape[0], b.shape[1], b.shape[2] * 2
+            if tuple(s.shape) != (E, n, k // 32) or k % 32:
+                raise RuntimeError("scales must be [E, out, in / 32]")
+            b, s = b.contiguous(), s.contiguous()              # the repack reads row-major through the raw pointers
+            tb, ts = torch.empty_like(b), torch.empty_like(s)
+            _check(lib.mi355_moe_mxfp4_tile_repack(_dev(b), _dev(s), _dev(tb), _dev(ts), E, n, k, _stream()), "moe_mxfp4_tile_repack")
+            self.w[which] = (tb, ts, n, k)
+        self.n_expert = gate_up_blocks.shape[0]
+        if down_blocks.shape[0] != self.n_expert:
+            raise RuntimeError("gate|up and down must hold the same experts")
+
+    def gemm(self, x, topk_ids, *, which, topk_weights=None, epilogue=EPI_STORE, out=None):
+        """x [T, k] with topk_ids [T, top_k] (one row per token) or [T * top_k, k] (one row per pair) -> [T * top_k, n]
+        (EPI_SILU_MUL: n / 2); topk_ids int32, topk_weights f32 of the same shape or None"""
+        tb, ts, n, k = self.w[which]
+        x2 = x.reshape(-1, k)
+        T, top_k = topk_ids.shape
+        if topk_ids.dtype != torch.int32 or (topk_weights is not None and topk_weights.dtype != torch.float32):
+            raise RuntimeError("topk_ids must be int32 and topk_weights float32")
+        if x2.shape[0] not in (T, T * top_k):
+            raise RuntimeError("x must have one row per token or one row per (token, expert) pair")
+        x_div = top_k if x2.shape[0] == T else 1
+        if out is None:
+            out = torch.empty((T * top_k, n // 2 if epilogue == EPI_SILU_MUL else n), dtype=x.dtype, device=x.device)
+        _check(lib.mi355_moe_gemm_mxfp4(_dev(out), _dev(x2), _dev(tb), _dev(ts), _dev(topk_ids),
+                                        _dev(topk_weights) if topk_weights is not None else None, T, top_k, self.n_expert, x_div,
+                                        n, k, 32, _DT[x.dtype], epilogue, _stream()), "moe_gemm_mxfp4")
+        return out
+
+    def forward(self, x, topk_ids, topk_weights):
+        """`forward_with_routing` (moe.rs:1782-1835): gate|up with the activation fused, down with the routing weights, then the sum
+        over a token's top_k rows (a torch reduction: it is not part of moe_gemm_mxfp4 and reads no weight)"""
+        T, top_k = topk_ids.shape
+        act = self.gemm(x, topk_ids, which="gate_up", epilogue=EPI_SILU_MUL)
+        y = self.gemm(act, topk_ids, which="down", topk_weights=topk_weights)
+        return y.view(T, top_k, -1).sum(1)
+
+
 class Nvfp4Linear:
     """`LnNvfp4` (linear.rs:1760-1943): blocks [out, in/2] uint8 (two e2m1 codes per byte, low nibble first) + e4m3fn scales
     [out, in/16] uint8 + the f32 multiplier the reference ends up with (1 / weight_global_scale, or weight_scale_2, or 1.0); re-ordered

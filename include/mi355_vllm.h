@@ -456,6 +456,27 @@ int mi355_mxfp4_tile_repack(const void* in_blocks, const void* in_scales, void* 
 int mi355_mxfp4_linear_tiled(void* out, const void* x, const void* w_tiled, const void* s_tiled,
                              const void* bias, const void* residual, int32_t num_tokens, int32_t n, int32_t k,
                              int32_t group, int32_t dtype, int32_t epilogue, int64_t stream);
+/* `FusedMoeMxfp4::forward_with_routing` (layers/moe.rs:1782-1835): its two `moe::moe_gemm_mxfp4` calls (moe.rs:1802-1827), a grouped
+ * W4A16 GEMM over the experts with the routing done on the device.  With P = num_tokens * top_k pairs and e_p = topk_ids[p], out is [P, n]:
+ *   out[p, r] = round_dt( w_p * sum_c x[p / x_div, c] * e2m1(B[e_p][r, c]) * 2^(S[e_p][r, c/32] - 127) )
+ * w_p = topk_weights[p], or 1 when topk_weights is NULL; it multiplies the f32 sum before the single rounding.  x_div == top_k: x has one
+ * row per token (the gate|up call); x_div == 1: one row per pair (the down call).  x / out in `dtype` (BF16 / F16), topk_ids [P] i32,
+ * topk_weights [P] f32.  MI355_EPI_STORE stores; MI355_EPI_SILU_MUL takes each expert's image as that of its packed [gate; up] matrix
+ * (moe.rs:1739-1741; n % 32 == 0, no topk_weights), rounds gate and up to `dtype` and writes silu(gate) * up as mi355_mxfp4_linear_tiled
+ * does: out is [P, n/2].  moe_gemm_mxfp4 itself lives in attention-rs, outside the reference tree: these rounding points are this
+ * library's choice.  No bias (the reference passes None).  w_tiled / s_tiled: the experts' tile images back to back (n * k/2 and
+ * n * k/32 bytes each), as mi355_moe_mxfp4_tile_repack (moe.rs:1734-1744, load time) writes them from blocks [E][n][k/2] and scales
+ * [E][n][k/32]: mi355_mxfp4_tile_repack over every expert in one launch.  A scale code 0xFF makes the outputs of its row NaN for the
+ * pairs of its expert only.  A pair whose id is outside [0, n_expert) (an expert of another rank) reads no weight and its out row is
+ * written as zeros.  Everything runs on `stream` without a host round trip; the plan's work space grows on the first call of a shape
+ * (a call inside a stream capture that would have to grow it returns hipErrorStreamCaptureUnsupported).  Served: n % 16 == 0,
+ * k % 128 == 0, group == 32, n_expert <= 4096; refused before any launch with hipErrorNotSupported / hipErrorInvalidValue: those, a dtype
+ * other than BF16 / F16, top_k < 1, n_expert < 1, x_div not in {1, top_k}, another epilogue, null pointers.  num_tokens == 0 returns 0. */
+int mi355_moe_mxfp4_tile_repack(const void* in_blocks, const void* in_scales, void* out_tiles, void* out_scales,
+                                int32_t n_expert, int32_t n, int32_t k, int64_t stream);
+int mi355_moe_gemm_mxfp4(void* out, const void* x, const void* w_tiled, const void* s_tiled, const int32_t* topk_ids,
+                         const float* topk_weights, int32_t num_tokens, int32_t top_k, int32_t n_expert, int32_t x_div,
+                         int32_t n, int32_t k, int32_t group, int32_t dtype, int32_t epilogue, int64_t stream);
 /* `LnNvfp4::forward` (linear.rs:1760-1943; selected at :1375-1397, :1526-1554): NVFP4 checkpoints (`quant_method: "nvfp4"`, ModelOpt /
  * compressed-tensors exports).  blocks is [n, k/2] bytes in MXFP4's coding (element 2j in the LOW nibble of byte j), scales is [n, k/16]
  * e4m3fn bytes, one per 16 k, and global_scale is the f32 MULTIPLIER the reference ends up with (1 / weight_global_scale, or
