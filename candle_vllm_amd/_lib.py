@@ -133,6 +133,8 @@ _sig("mi355_mxfp4_tile_repack", ctypes.c_int, [c_vp] * 4 + [c_i32, c_i32, c_i64]
 _sig("mi355_mxfp4_linear_tiled", ctypes.c_int, [c_vp] * 6 + [c_i32] * 6 + [c_i64])
 _sig("mi355_moe_mxfp4_tile_repack", ctypes.c_int, [c_vp] * 4 + [c_i32, c_i32, c_i32, c_i64])
 _sig("mi355_moe_gemm_mxfp4", ctypes.c_int, [c_vp] * 6 + [c_i32] * 9 + [c_i64])
+_sig("mi355_moe_fp8_tile_repack", ctypes.c_int, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i64])
+_sig("mi355_moe_gemm_fp8", ctypes.c_int, [c_vp] * 6 + [c_i32] * 11 + [c_i64])
 _sig("mi355_nvfp4_tile_repack", ctypes.c_int, [c_vp] * 4 + [c_i32, c_i32, c_i64])
 _sig("mi355_nvfp4_linear_tiled", ctypes.c_int, [c_vp] * 6 + [c_i32] * 4 + [c_f32] * 2 + [c_i32, c_i32, c_i64])
 

@@ -730,6 +730,58 @@ class Mxfp4MoE:
         return y.view(T, top_k, -1).sum(1)
 
 
+class Fp8MoE:
+    """`FusedMoeFp8` (layers/moe.rs:908-1481): the experts' packed gate|up weights [E, 2I, H] and down weights [E, H, I] (uint8 e4m3fn
+    bytes) with their f32 block scales [E, 2 * ceil(I/128), H/128] (`cat(gate_scale, up_scale)`, moe.rs:1385-1386) / [E, ceil(H/128),
+    I/128]; re-ordered into the experts' tile images at construction.  `gemm` is one `moe_gemm_fp8` call (routing on the device, no host
+    round trip), `forward` is `forward_with_routing`."""
+
+    def __init__(self, gate_up_weight, gate_up_scale, down_weight, down_scale, block_size=(128, 128)):
+        self.w = {}
+        self.block_n, self.block_k = block_size
+        for which, w, s in (("gate_up", gate_up_weight, gate_up_scale), ("down", down_weight, down_scale)):
+            if w.dtype != torch.uint8 or s.dtype != torch.float32 or w.dim() != 3:
+                raise RuntimeError("Fp8MoE takes uint8 e4m3fn weights [E, out, in] and f32 block scales")
+            E, n, k = w.shape
+            n_half = n // 2 if which == "gate_up" else 0       # each half of the packed matrix has scale rows of its own
+            sr = 2 * -(-n_half // self.block_n) if n_half else -(-n // self.block_n)
+            if tuple(s.shape) != (E, sr, -(-k // self.block_k)):
+                raise RuntimeError(f"{which} scales must be [E, {sr}, ceil(in / block)]")
+            w = w.contiguous()                                 # the repack reads row-major through the raw pointer
+            tw = torch.empty_like(w)
+            _check(lib.mi355_moe_fp8_tile_repack(_dev(w), _dev(tw), E, n, k, _stream()), "moe_fp8_tile_repack")
+            self.w[which] = (tw, s.contiguous(), n, k, n_half)
+        self.n_expert = gate_up_weight.shape[0]
+        if down_weight.shape[0] != self.n_expert:
+            raise RuntimeError("gate|up and down must hold the same experts")
+
+    def gemm(self, x, topk_ids, *, which, topk_weights=None, epilogue=EPI_STORE, out=None):
+        """x [T, k] with topk_ids [T, top_k] (one row per token) or [T * top_k, k] (one row per pair) -> [T * top_k, n]
+        (EPI_SILU_MUL: n / 2); topk_ids int32, topk_weights f32 of the same shape or None"""
+        tw, s, n, k, n_half = self.w[which]
+        x2 = x.reshape(-1, k)
+        T, top_k = topk_ids.shape
+        if topk_ids.dtype != torch.int32 or (topk_weights is not None and topk_weights.dtype != torch.float32):
+            raise RuntimeError("topk_ids must be int32 and topk_weights float32")
+        if x2.shape[0] not in (T, T * top_k):
+            raise RuntimeError("x must have one row per token or one row per (token, expert) pair")
+        x_div = top_k if x2.shape[0] == T else 1
+        if out is None:
+            out = torch.empty((T * top_k, n // 2 if epilogue == EPI_SILU_MUL else n), dtype=x.dtype, device=x.device)
+        _check(lib.mi355_moe_gemm_fp8(_dev(out), _dev(x2), _dev(tw), _dev(s), _dev(topk_ids),
+                                      _dev(topk_weights) if topk_weights is not None else None, T, top_k, self.n_expert, x_div,
+                                      n, k, n_half, self.block_n, self.block_k, _DT[x.dtype], epilogue, _stream()), "moe_gemm_fp8")
+        return out
+
+    def forward(self, x, topk_ids, topk_weights):
+        """`forward_with_routing` (moe.rs:1429-1481): gate|up with the activation fused (n_half = I), down with the routing weights
+        (n_half = 0), then the sum over a token's top_k rows (a torch reduction: it is not part of moe_gemm_fp8 and reads no weight)"""
+        T, top_k = topk_ids.shape
+        act = self.gemm(x, topk_ids, which="gate_up", epilogue=EPI_SILU_MUL)
+        y = self.gemm(act, topk_ids, which="down", topk_weights=topk_weights)
+        return y.view(T, top_k, -1).sum(1)
+
+
 class Nvfp4Linear:
     """`LnNvfp4` (linear.rs:1760-1943): blocks [out, in/2] uint8 (two e2m1 codes per byte, low nibble first) + e4m3fn scales
     [out, in/16] uint8 + the f32 multiplier the reference ends up with (1 / weight_global_scale, or weight_scale_2, or 1.0); re-ordered

@@ -477,6 +477,32 @@ int mi355_moe_mxfp4_tile_repack(const void* in_blocks, const void* in_scales, vo
 int mi355_moe_gemm_mxfp4(void* out, const void* x, const void* w_tiled, const void* s_tiled, const int32_t* topk_ids,
                          const float* topk_weights, int32_t num_tokens, int32_t top_k, int32_t n_expert, int32_t x_div,
                          int32_t n, int32_t k, int32_t group, int32_t dtype, int32_t epilogue, int64_t stream);
+/* `FusedMoeFp8::forward_with_routing` (layers/moe.rs:1429-1481): its two `moe_gemm_fp8` calls (moe.rs:1447-1473), a grouped W8A16 GEMM
+ * over the experts' e4m3fn weights with one f32 scale per 128 x 128 block, the routing done on the device.  With P = num_tokens * top_k
+ * pairs and e_p = topk_ids[p], out is [P, n]:
+ *   out[p, r] = round_dt( w_p * sum_kb s[e_p][srow(r)][kb] * sum_{c in kb} x[p / x_div, c] * e4m3(W[e_p][r, c]) )
+ * w_p, x_div, topk_ids, topk_weights, the out-of-range-id rule (such a pair reads no weight, its out row is written as zeros) and the
+ * capture rule (growth of the plan work space inside a capture returns hipErrorStreamCaptureUnsupported) are mi355_moe_gemm_mxfp4's;
+ * num_tokens == 0 returns 0.  Numerics are mi355_fp8_linear_tiled's: the weight bytes decode exactly, the activations stay 16-bit,
+ * accumulation is f32 with the block scale applied in f32 once per (16-row tile, 128 k); w_p multiplies the f32 sum before the single
+ * rounding.  MI355_EPI_SILU_MUL takes each expert's image as that of its packed [gate; up] matrix (moe.rs:1385; n % 32 == 0, no
+ * topk_weights, n_half == n / 2), rounds gate and up to `dtype` and writes silu(gate) * up as mi355_fp8_linear_tiled does without a bias:
+ * out is [P, n/2].  moe_gemm_fp8 itself lives in attention-rs, outside the reference tree: these rounding points are this library's choice.
+ * w_scale is [n_expert][SR][k/128] f32 in checkpoint order; n_half tells how scale rows map onto weight rows.  n_half == 0 (the down
+ * call): SR = ceil(n / 128), srow(r) = r / 128.  n_half == n / 2 (the gate|up call, with or without the fused activation): the scales
+ * are cat(gate_scale, up_scale) (moe.rs:1230-1231, 1385-1386), each half with ceil(n_half / 128) scale rows of its own: SR = 2 *
+ * ceil(n_half / 128), srow(r) = (r / n_half) * ceil(n_half / 128) + (r % n_half) / 128.  The NaN codes 0x7f / 0xff decode to NaN: they
+ * poison their weight row for the pairs of their expert only.  No K limit.  Served: n % 16 == 0, k % 128 == 0, block_n == block_k == 128,
+ * n_expert <= 4096, BF16 / F16; refused before any launch with hipErrorNotSupported / hipErrorInvalidValue, out untouched: those, top_k < 1,
+ * n_expert < 1, x_div not in {1, top_k}, n_half not in {0, n / 2} or n_half % 16 != 0, SILU_MUL with n % 32 != 0 / with topk_weights /
+ * with n_half != n / 2, another epilogue, null pointers.
+ * mi355_moe_fp8_tile_repack (moe.rs:1378-1386, load time): weights [n_expert][n][k] bytes -> the experts' tile images back to back
+ * (n * k bytes each): mi355_fp8_tile_repack over every expert in one launch; device to device, in != out. */
+int mi355_moe_fp8_tile_repack(const void* in, void* out, int32_t n_expert, int32_t n, int32_t k, int64_t stream);
+int mi355_moe_gemm_fp8(void* out, const void* x, const void* w_tiled, const float* w_scale, const int32_t* topk_ids,
+                       const float* topk_weights, int32_t num_tokens, int32_t top_k, int32_t n_expert, int32_t x_div,
+                       int32_t n, int32_t k, int32_t n_half, int32_t block_n, int32_t block_k, int32_t dtype,
+                       int32_t epilogue, int64_t stream);
 /* `LnNvfp4::forward` (linear.rs:1760-1943; selected at :1375-1397, :1526-1554): NVFP4 checkpoints (`quant_method: "nvfp4"`, ModelOpt /
  * compressed-tensors exports).  blocks is [n, k/2] bytes in MXFP4's coding (element 2j in the LOW nibble of byte j), scales is [n, k/16]
  * e4m3fn bytes, one per 16 k, and global_scale is the f32 MULTIPLIER the reference ends up with (1 / weight_global_scale, or
